@@ -12,11 +12,18 @@ and the layer's parameter gradients are all-reduced over RCCL (csa_amd.train's b
 reducer, DDP semantics), the one exchange of script/train.py:83,109. value = ASTs processed by all
 ranks / max-over-ranks wall time.
 
-Printed JSON line (rank 0): contract fields + "roofline" for the dominant kernel (HIP events
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+JSON line (rank 0) with the contract fields: metric, value, unit, higher_is_better, dtype, ms_per_step.
+`--dump-outputs DIR` also writes what the last timed step computed (X, sparsity, the input and parameter
+gradients) as DIR/<name>.npy in float32; inputs and Philox keys are seeded, so the same arguments give the
+same inputs in every run.
+
+`--full` adds everything else to the line: "roofline" for the dominant kernel (HIP events
 recorded around that kernel's launch on its stream, every timed step; the dominant kernel and the
 per-stage "stage_ms" come from an untimed pass with events around every stage, so the timed steps
-carry only the two events of one kernel) + "cpu_baseline" (the oracle restatement of the reference
-op sequence on the host CPU, rank 0 at N=1).
+carry only the two events of one kernel), the bf16 / padded-mask / CSE / dense / long-AST legs, the
+train-step legs and "cpu_baseline" (the oracle restatement of the reference op sequence on the host
+CPU, rank 0 at N=1). The --no-* options switch single legs of a --full run off.
 """
 import argparse
 import ctypes
@@ -153,6 +160,28 @@ def host_cpu_info():
 def progress(msg):
     """One stderr line per bench leg, so a long default run is never silent for minutes."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20  # --dump-outputs: float32 bytes over all files (the option's limit is 64 MB)
+
+
+def dump_outputs(dirname, per_item, whole, n_items):
+    """--dump-outputs: `whole` arrays as they are; of the `per_item` arrays (leading dimension = the batch) the
+    same seeded sample of batch elements for all of them, as many as the byte budget allows. One float32
+    DIR/<name>.npy per array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    per_item = {n: t for n, t in per_item.items() if t is not None}
+    whole = {n: t for n, t in whole.items() if t is not None}
+    item_bytes = sum(4 * t[0].numel() for t in per_item.values())
+    left = DUMP_BUDGET_BYTES - sum(4 * t.numel() for t in whole.values())
+    keep = max(1, min(n_items, left // max(item_bytes, 1)))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n_items, keep, replace=False)))
+    for n, t in whole.items():
+        np.save(os.path.join(dirname, n + ".npy"), t.detach().float().cpu().numpy())
+    for n, t in per_item.items():
+        np.save(os.path.join(dirname, n + ".npy"), t.detach().index_select(0, idx.to(t.device)).float().cpu().numpy())
+    return sorted(list(whole) + list(per_item))
 
 
 def pick_threads(step, info):
@@ -439,13 +468,19 @@ def launcher_selftest(args, world, rank, dev):
     model = BucketedDataParallel(lin) if world > 1 else lin
     x = torch.randn(32, 64)
 
+    last = {}
+
     def step(i):
         lin.zero_grad(set_to_none=True)
-        model(x).square().mean().backward()
+        y = model(x)
+        y.square().mean().backward()
+        last["y"] = y
 
     for i in range(args.warmup):
         step(i)
     el = timed_region(world, dev, args.steps, step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": last["y"]}, {"grad_" + n: p.grad for n, p in lin.named_parameters()}, 32)
     return {"metric": "launcher self-test (data-parallel Linear on CPU/gloo; not the hot path)", "value": round(world * 32 *
             args.steps / el, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(el * 1000 / args.steps, 4), "higher_is_better": True, "scaling": "weak",
@@ -491,10 +526,13 @@ def padded_lengths(B, N, rank):
     return torch.randint(min(50, N), N + 1, (B,), generator=gpad)
 
 
-def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision, eval_, reducer="torch", padded=False):
+def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision, eval_, reducer="torch", padded=False,
+                  profile=True):
     """One SBMAttention (or FullAttention) fwd+bwd step on synthetic inputs resident in HBM: an untimed pass with
     HIP events around every stage (per-stage kernel times, the dominant stage), then the timed region with events
-    only around the dominant kernel's launch (its live average launch duration). Returns the pieces of the line."""
+    only around the dominant kernel's launch (its live average launch duration). profile=False: the same steps
+    without any event (the profiling pass's steps run plain, so the timed region starts equally warm). Returns the pieces of the line; "outputs" holds what the last timed step
+    returned and the tensors its gradients went to."""
     from csa_amd import ops
     from csa_amd._lib import STAGES, KERNEL_OF_STAGE
     from csa_amd.module.sbm_attn import FullAttention, SBMAttention
@@ -531,17 +569,43 @@ def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision,
             torch.autograd.backward([X], [dX])
         else:
             torch.autograd.backward([X, sp], [dX, dsp])
+        return X, sp
+
+    last = {}
+
+    def outputs():
+        X, sp = last["out"]
+        return {"per_ast": {"X": X, "dQ": Q.grad, "dK": K.grad, "dV": V.grad},
+                "whole": dict({"sparsity": sp}, **{"grad_" + n: p.grad for n, p in mod.named_parameters()})}
 
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
+    flops = stage_flops_per_ast(H, N, N, d, 0 if dense else k)
+    if dense:
+        flops = {"attn_fwd": H * 4 * N * N * d, "attn_bwd_q": H * 2 * N * N * d, "attn_bwd_kv": H * 6 * N * N * d}
+    # untimed steps between the warm-up and the timed region: the per-stage profiling pass, or as many plain steps,
+    # so both kinds of run start their timed steps after the same number of steps on the device
+    nprof = max(3, min(steps, 10))
+    if not profile:
+        for _ in range(nprof):
+            step()
+
+        def plain_step(i):
+            out = step()
+            if i == steps - 1:
+                last["out"] = out
+
+        elapsed = timed_region(world, dev, steps, plain_step)
+        return {"mod": mod, "step": step, "mask": mask, "stage_ms": {}, "flops": flops, "timed": {}, "over": set(),
+                "overlapped": False, "dom": None, "dom_ms": None, "kernel_of": dict(KERNEL_OF_STAGE),
+                "elapsed": elapsed, "roofline": None, "outputs": outputs}
     ev, make_profs_, stage_times_ = stage_profilers()
     fwd_stages = ("prep", "proj_fwd", "attn_fwd")
     make_profs = lambda n, stages: make_profs_(n, stages, STAGES, fwd_stages)  # noqa: E731
     stage_times = lambda profs, stages: stage_times_(profs, stages, STAGES, fwd_stages)  # noqa: E731
 
     # 1) untimed profiling pass: HIP events around every stage -> per-stage kernel times (diagnostic)
-    nprof = max(3, min(steps, 10))
     profs = make_profs(nprof, list(STAGES))
     for i in range(nprof):
         ops.set_stage_profiler(*profs[i])
@@ -549,9 +613,6 @@ def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision,
     ops.set_stage_profiler(None, None)
     torch.cuda.synchronize()
     stage_ms = stage_times(profs, list(STAGES))
-    flops = stage_flops_per_ast(H, N, N, d, 0 if dense else k)
-    if dense:
-        flops = {"attn_fwd": H * 4 * N * N * d, "attn_bwd_q": H * 2 * N * N * d, "attn_bwd_kv": H * 6 * N * N * d}
     if "proj_bwd_k" in stage_ms:  # concurrent schedule: the projection backward's key / query items split
         flops["proj_bwd_k"] = H * (N * (12 * d * d + 4 * k * d) + N * 4 * k * k)
         flops["proj_bwd"] = H * N * (12 * d * d + 4 * k * d)
@@ -580,7 +641,9 @@ def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision,
 
     def timed_step(i):
         ops.set_stage_profiler(*profs[i])
-        step()
+        out = step()
+        if i == steps - 1:
+            last["out"] = out
 
     elapsed = timed_region(world, dev, steps, timed_step)
     ops.set_stage_profiler(None, None)
@@ -597,7 +660,7 @@ def measure_layer(world, rank, dev, steps, warmup, B, N, d, k, dense, precision,
                                   "present, uses the committed rocprofv3 kernel-trace average)"}
     return {"mod": mod, "step": step, "mask": mask, "stage_ms": stage_ms, "flops": flops, "timed": timed,
             "over": over, "overlapped": bool(over), "dom": dom, "dom_ms": dom_ms, "kernel_of": kernel_of,
-            "elapsed": elapsed, "roofline": roofline}
+            "elapsed": elapsed, "roofline": roofline, "outputs": outputs}
 
 
 def rocprof_frac(table, leg, kernel, flops_per_launch):
@@ -728,6 +791,13 @@ def main():
     ap.add_argument("--eval", action="store_true", help="eval mode (no dropout)")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
                     help="operand precision of the attention contractions (fp32 = the reference's)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-stage profiling pass and roofline, the bf16 / padded-mask / CSE / "
+                         "dense / long-AST legs, the train-step legs and the CPU baselines (each can be switched off "
+                         "with its --no-* option); without --full only the headline measurement runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (X, sparsity, input and "
+                         "parameter gradients; a seeded sample of the batch within 64 MB) as DIR/<name>.npy, float32")
     ap.add_argument("--no-bf16-leg", action="store_true", help="skip the bf16-mode side measurement")
     ap.add_argument("--no-padded-leg", action="store_true", help="skip the padded-mask (n_b ~ U[50,150]) leg")
     ap.add_argument("--padded", action="store_true",
@@ -775,7 +845,14 @@ def main():
     B, H, N, d, k = args.batch, 8, args.seq_len, args.head_dim, args.clusters
     progress(f"SBM layer B={B} N={N} d={d} k={k}: warm-up")
     L = measure_layer(world, rank, dev, args.steps, args.warmup, B, N, d, k, args.dense, args.precision, args.eval,
-                      reducer=args.reducer, padded=args.padded)
+                      reducer=args.reducer, padded=args.padded, profile=args.full)
+    outputs = L.pop("outputs")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        o = outputs()
+        dumped = dump_outputs(args.dump_outputs, o["per_ast"], o["whole"], B)
+        del o
+    del outputs  # the last step's X is not kept beyond the dump
     mod, step, mask = L["mod"], L["step"], L["mask"]
     stage_ms, flops, timed, over, overlapped = L["stage_ms"], L["flops"], L["timed"], L["over"], L["overlapped"]
     dom, dom_ms, kernel_of, elapsed = L["dom"], L["dom_ms"], L["kernel_of"], L["elapsed"]
@@ -783,7 +860,7 @@ def main():
     value = world * B * args.steps / elapsed
     roofline = L["roofline"]
     headline = (B, N, d, k, args.precision, args.dense, args.eval, args.padded) == (256, 150, 64, 10, "fp32", False, False, False)
-    table = pmc_table() if headline else None
+    table = pmc_table() if headline and args.full else None
     if roofline and table:
         tr = table["kernels"].get(kernel_of[dom])
         if tr:  # HBM bytes per launch and rocprof duration from the shipped PMC table (tools/pmc_traffic.py)
@@ -818,9 +895,14 @@ def main():
         "bwd_schedule": ("projection backward key-block items on a side stream beside k_attn_bwd_qg (overlapped "
                          "stage windows: " + ", ".join(sorted(over)) + ")") if overlapped else "in order",
     }
+    if not args.full:  # no profiling pass ran: the line carries the headline measurement alone
+        for key in ("roofline", "stage_ms", "stage_frac_of_f32_mfma_peak", "bwd_schedule"):
+            del out[key]
+    if dumped:
+        out["dumped_outputs"] = dumped
     if table:
         out.update(traffic_evidence(table, B, stage_ms))
-    if args.precision == "fp32" and not args.no_bf16_leg and not args.dense and N <= 150:
+    if args.full and args.precision == "fp32" and not args.no_bf16_leg and not args.dense and N <= 150:
         # the same layer with CSA_DTYPE_BF16 (north_star's bf16 variant): side measurement, same step
         progress("bf16-mode leg")
         mod.attn_precision = "bf16"
@@ -841,7 +923,7 @@ def main():
             "frac_at_bf16_io": round(vb * IDEAL_BYTES_PER_AST_BF16IO / 1e9 / PEAK_HBM_GBS, 4),
             "note": "ideal fused bytes per AST x ASTs/s against 8 TB/s (SURVEY 8(d) config 2); frac with the "
                     "fp32 I/O the mode takes and returns, frac_at_bf16_io with 2.05 MB/AST bf16 I/O"}
-    if not args.dense and N == 150 and not args.no_padded_leg:
+    if args.full and not args.dense and N == 150 and not args.no_padded_leg:
         # config 2's real batches are padded: n_b ~ U[50, 150] nodes per AST, the rest key-masked (same layer, B)
         progress("padded-mask leg")
         nb = padded_lengths(B, N, rank)
@@ -856,7 +938,7 @@ def main():
                               "note": "config 2 padded batches: n_b ~ U[50,150] real nodes per AST (seeded), key mask "
                                       "1 on the padding; fully masked 32-key tiles take the attention kernels' light "
                                       "paths (STE term only), the projection runs every row"}
-    if world == 1 and headline and not args.no_side_legs:
+    if args.full and world == 1 and headline and not args.no_side_legs:
         # BASELINE's other kernel configurations beside the headline, each with its dominant kernel's live roofline
         progress("CSE leg (java relation attention, B=64)")
         out["cse"] = cse_leg(dev, args.steps, args.warmup, table)
@@ -868,7 +950,7 @@ def main():
             progress(f"long-AST leg (config 5: N=1024, k={kk}, B=16)")
             out["long_ast"][f"k{kk}"] = side_layer_leg(dev, max(5, args.steps // 2), max(2, args.warmup // 2), 16,
                                                        1024, 64, kk, False, table, f"long_k{kk}")
-    if not args.no_train:
+    if args.full and not args.no_train:
         progress("train-step leg (config/java.py, 64 ASTs per GPU)")
         from csa_amd.train import GEMM_TABLE, use_tuned_gemms
         ntuned = use_tuned_gemms(not args.default_gemms)
@@ -899,7 +981,7 @@ def main():
                 out["train_default_gemms"] = {k: v for k, v in train_step_bench(
                     world, rank, dev, args.train_steps, args.train_warmup).items()
                     if k in ("ms_per_step", "samples_per_s", "mean_loss")}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("CPU baseline (oracle SBM layer on host cores)")
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, B=B if N <= 150 else 1, N=N, k=k)
         if not args.no_cpu_config1:

@@ -30,6 +30,21 @@ def test_bench_single_rank_default():
     assert out["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_and_full_option(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy, the same from run to run; --full is
+    accepted (the self-test has no further legs) and --steps sets the timed steps of the line."""
+    import numpy as np
+    a, b = tmp_path / "a", tmp_path / "b"
+    out = _run("--dump-outputs", str(a))
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    _run("--full", "--dump-outputs", str(b))
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["grad_bias.npy", "grad_weight.npy", "y.npy"] == sorted(p.name for p in b.iterdir())
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y), n
+
+
 def test_bench_rejects_world_size_mismatch():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--device", "cpu", "--gpus", "2"],

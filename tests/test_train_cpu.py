@@ -95,6 +95,7 @@ def _worker(rank, world, port, q, cases, steps):
                       LOCAL_RANK=str(rank))
     from csa_amd.model import label_smoothing_loss
     from csa_amd.train import AdamW, BucketedDataParallel, init_distributed, make_train_step, wrap_ddp
+    torch.cuda.is_available = lambda: False  # the gloo / host path is the one under test, also on a box with GPUs
     r, w, _, dev = init_distributed()
     out = {}
     for impl, cap_mb in cases:
@@ -210,6 +211,7 @@ def _worker_unused(rank, world, port, q, steps):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     from csa_amd.train import BucketedDataParallel, init_distributed
+    torch.cuda.is_available = lambda: False  # gloo on host tensors, also on a box with GPUs
     init_distributed()
     torch.manual_seed(0)
     model = Branchy()

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 TAG=${1:-x}
 OUT=$R/gpurun_out/cap_$TAG
 mkdir -p $OUT
-CMD="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-bf16-leg"
+CMD="python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-bf16-leg"
 cd /tmp
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $CMD > $OUT/stats.log 2>&1 || exit $?
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $CMD > $OUT/fetch.log 2>&1 || exit $?
@@ -16,7 +16,7 @@ timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write
 cd $R
 H=$(python3 -c "import sys; sys.path.insert(0,'code-structure-aware-transformer_amd'); from csa_amd.build import source_hash; print(source_hash())")
 python3 tools/pmc_traffic.py $OUT/fetch/run_counter_collection.csv $OUT/write/run_counter_collection.csv \
-  $OUT/stats/run_kernel_stats.csv --source-hash "$H" --cmd "bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-bf16-leg" > $OUT/pmc_gfx950.json || exit $?
+  $OUT/stats/run_kernel_stats.csv --source-hash "$H" --cmd "bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-bf16-leg" > $OUT/pmc_gfx950.json || exit $?
 python3 - $OUT/pmc_gfx950.json <<'PY'
 import json, sys
 t = json.load(open(sys.argv[1]))

@@ -11,5 +11,5 @@ timeout -k 10 900 python -u -m pytest $TESTS -m gpu -x -v -s --timeout 300 --tim
 grep -E "PASS|FAIL|ERROR" "$OUT/pytest.log" | tail -5; tail -3 "$OUT/pytest.log"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { cat "$OUT/smoke.log"; exit 1; }
 cat "$OUT/smoke.log"
-timeout -k 10 400 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 400 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 cat "$OUT/bench.json"

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("fetch")
     ap.add_argument("write")
     ap.add_argument("stats")
-    ap.add_argument("--cmd", default="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-bf16-leg")
+    ap.add_argument("--cmd", default="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-bf16-leg")
     ap.add_argument("--source-hash", default="")
     ap.add_argument("--leg", action="append", default=[],
                     help="NAME=kernel_stats.csv of a side-leg run (bench.py's cse / dense / long_k* roofline legs)")
