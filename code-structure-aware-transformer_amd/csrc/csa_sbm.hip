@@ -1358,7 +1358,9 @@ __device__ __forceinline__ void attn_fwd_item(const KArgs& p, float* __restrict_
   const float n = Zg / Z;
   const float Dn = fmaxf(n, NORM_EPS);
   const float dscale = DROP ? 1.f / (1.f - p.attn_p) : 1.f;  // dropout's 1/(1-p), applied once per row
-  const float inv = dscale / (Z * Dn);
+  // Z == 0: every key of the AST is masked (any valid key leaves Z > 0). The reference's 0/0 there is NaN;
+  // the kernels return X = 0 and an lse of +inf, so that the backward's P = exp(s - lse) is 0 and dK = dV = 0.
+  const float inv = Z > 0.f ? dscale / (Z * Dn) : 0.f;
   if (iv) {
     float* xo = p.X + b * p.x_sb + hd * p.x_sh + (int64_t)i * p.x_sn;
 #pragma unroll
@@ -1371,7 +1373,7 @@ __device__ __forceinline__ void attn_fwd_item(const KArgs& p, float* __restrict_
     store_rows<DT>(xo, D, D, o, true);
     if (h == 0) {
       f32x4 st;
-      st[0] = m_run + logf(Z);   // lse: P = exp(s - lse)
+      st[0] = Z > 0.f ? m_run + logf(Z) : INFINITY;  // lse: P = exp(s - lse)
       st[1] = 1.f / Dn;          // 1 / max(n, eps)
       st[2] = (n >= NORM_EPS) ? 1.f : 0.f;
       st[3] = 0.f;               // gamma, filled by the backward

@@ -97,6 +97,96 @@ def test_full_attention_oracle(golden, case):
         np.testing.assert_allclose(gg.numpy(), z[name], rtol=1e-4, atol=1e-5)
 
 
+@pytest.mark.parametrize("case", ["sbm_n37_mapgrad", "sbm_n33_d96_mapgrad"])
+def test_closed_form_map_gradients_match_autograd_fp64(golden, case):
+    """closed_form's dgraph / dattn arguments against sbm_ref.sbm_attention's autograd, both in fp64 on the same
+    (forced) graph: agreement at the fp64 level, and with the reference's fp32 golden gradients at 1e-4."""
+    z = golden(case)
+    B, H, N, d, k = (int(v) for v in z["meta"])
+    d64 = lambda n, grad=False: t(z[n]).double().requires_grad_(grad)
+    Q, K, V = d64("Q", True), d64("K", True), d64("V", True)
+    params = {k_[2:]: t(v).double().requires_grad_(True) for k_, v in z.items() if k_.startswith("p:")}
+    X, sp, graph, attn = sbm_ref.sbm_attention(Q, K, V, d64("mask"), params, d64("u"), k)
+    assert np.array_equal(graph.detach().numpy().astype(np.uint8), z["graph"])
+    ((X * d64("dX")).sum() + (sp * d64("dsparsity")).sum() + (graph * d64("dgraph")).sum()
+     + (attn * d64("dattn")).sum()).backward()
+    out, g = closed_form.sbm_fwd_bwd(t(z["Q"]), t(z["K"]), t(z["V"]), t(z["mask"]),
+                                     {n: p.detach() for n, p in params.items()}, t(z["u"]), k, t(z["dX"]),
+                                     t(z["dsparsity"]), graph_override=graph.detach(), dgraph=t(z["dgraph"]),
+                                     dattn=t(z["dattn"]), bf16=False)
+    ref = {"Q": Q.grad, "K": K.grad, "V": V.grad}
+    ref.update({n: p.grad for n, p in params.items()})
+    for n, r in ref.items():
+        np.testing.assert_allclose(g[n].numpy(), r.numpy(), rtol=1e-9, atol=1e-12 * float(r.abs().max()), err_msg=n)
+    for n, gn in (("dQ", "Q"), ("dK", "K"), ("dV", "V")):
+        np.testing.assert_allclose(g[gn].numpy(), z[n], rtol=1e-4, atol=1e-5, err_msg=n)
+
+
+@pytest.mark.parametrize("with_keep", [False, True])
+def test_dense_closed_form_matches_autograd_fp64(with_keep):
+    """closed_form.dense_fwd_bwd against sbm_ref.full_attention's autograd in fp64, with padded keys, an upstream
+    attn gradient, and with / without an attention-dropout multiplier."""
+    g = torch.Generator().manual_seed(17)
+    B, H, N, d = 2, 2, 45, 64
+    Q, K, V, dX = (torch.randn(B, H, N, d, generator=g, dtype=torch.float64) for _ in range(4))
+    dattn = torch.randn(B, H, N, N, generator=g, dtype=torch.float64)
+    mask = torch.zeros(B, N, dtype=torch.float64)
+    mask[1, 30:] = 1.0
+    keep = (torch.rand(B, H, N, N, generator=g) < 0.8).double() / 0.8 if with_keep else None
+    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
+    X, _, _, attn = sbm_ref.full_attention(q, k, v, mask, attn_keep=keep)
+    ((X * dX).sum() + (attn * dattn).sum()).backward()
+    out, gr = closed_form.dense_fwd_bwd(Q, K, V, mask, dX, attn_keep=keep, dattn=dattn)
+    np.testing.assert_allclose(out["X"].numpy(), X.detach().numpy(), rtol=1e-9, atol=1e-13)
+    np.testing.assert_allclose(out["attn"].numpy(), attn.detach().numpy(), rtol=1e-9, atol=1e-13)
+    for n, r in (("Q", q.grad), ("K", k.grad), ("V", v.grad)):
+        np.testing.assert_allclose(gr[n].numpy(), r.numpy(), rtol=1e-9, atol=1e-12 * float(r.abs().max()), err_msg=n)
+
+
+@pytest.mark.parametrize("case", ["full_n37", "full_n37_mapgrad"])
+def test_dense_closed_form_matches_reference(golden, case):
+    z = golden(case)
+    out, gr = closed_form.dense_fwd_bwd(t(z["Q"]), t(z["K"]), t(z["V"]), t(z["mask"]), t(z["dX"]),
+                                        dattn=t(z["dattn"]) if "dattn" in z else None)
+    np.testing.assert_allclose(out["X"].numpy(), z["X"], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(out["attn"].numpy(), z["attn"], rtol=1e-4, atol=1e-5)
+    for n, gn in (("dQ", "Q"), ("dK", "K"), ("dV", "V")):
+        np.testing.assert_allclose(gr[gn].numpy(), z[n], rtol=1e-4, atol=1e-5, err_msg=n)
+
+
+def test_closed_form_relu_tie_report_and_override():
+    """The ReLU-tie rule's oracle side: a pre-activation planted within TIE_FACTOR of its fp32 error bound is
+    reported (and nothing else is), and relu_override flips exactly that element's mask, which moves the
+    gradients; overriding it to the oracle's own choice changes nothing."""
+    g = torch.Generator().manual_seed(5)
+    B, H, N, d, k = 1, 2, 9, 64, 5
+    Q, K, V, dX = (torch.randn(B, H, N, d, generator=g) for _ in range(4))
+    params = {"layer.weight": torch.randn(H * k, d, generator=g)}
+    for i in (0, 3, 6):
+        params[f"proj.{i}.weight"] = 0.2 * torch.randn(d, d, generator=g)
+        params[f"proj.{i}.bias"] = 0.1 * torch.randn(d, generator=g)
+    u = torch.rand(B, H, N, N, generator=g)
+    args = (Q, K, V, torch.zeros(B, N), params, u, k, dX, torch.full((H,), 1e-3))
+    out, g0 = closed_form.sbm_fwd_bwd(*args)
+    assert out["relu_ties"] == []
+    z0, bd, _ = out["relu_pre"]["k0"]
+    idx = (0, 1, 4, 7)
+    # move the bias so that z0[idx] lands at 0.1 * 2^-24 * bound, well inside the tie band, on the positive side
+    params["proj.0.bias"] = params["proj.0.bias"].double()
+    params["proj.0.bias"][7] += -z0[idx] + 0.1 * 2.0 ** -24 * bd[idx]
+    out, g1 = closed_form.sbm_fwd_bwd(*args)
+    ties = [(key, i) for key, i, _ in out["relu_ties"]]
+    assert ("k0", idx) in ties and len(ties) <= 2 and all(i[-1] == 7 for _, i in ties)
+    graph = out["graph"]
+    _, same = closed_form.sbm_fwd_bwd(*args, graph_override=graph, relu_override={"k0": {idx: True}})
+    _, flip = closed_form.sbm_fwd_bwd(*args, graph_override=graph, relu_override={"k0": {idx: False}})
+    assert torch.equal(same["K"], g1["K"])
+    assert float((flip["K"][idx[:3]] - g1["K"][idx[:3]]).abs().max()) > 0
+    other = torch.ones(B, H, N, dtype=torch.bool)
+    other[idx[:3]] = False
+    assert torch.equal(flip["K"][other], g1["K"][other])  # dK of the other rows: untouched (row-local MLP)
+
+
 @pytest.mark.parametrize("case", ["attn_layer_n29", "attn_layer_full_n29"])
 def test_attention_layer_oracle(golden, case):
     z = golden(case)

@@ -1,4 +1,6 @@
 """GPU parity: fused SBM / dense attention kernels vs the reference's golden vectors and the oracle."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
@@ -267,10 +269,43 @@ def _rand_case(B, H, N, d, k, seed, pad=True):
     return Q, K, V, mask, u, dX, dsp, params
 
 
-def _run_module(Q, K, V, mask, u, dX, dsp, params, k, training=False):
+def _match_oracle_up_to_relu_ties(run_oracle, check):
+    """The ReLU-tie rule. run_oracle(relu_override) -> closed_form.sbm_fwd_bwd's (out, grads); check(out, grads)
+    asserts the GPU result against them on every compared tensor at once.
+
+    A projection-MLP pre-activation z within closed_form.TIE_FACTOR (8 * 2^-24) of its fp32 error bound
+    |R(x)| |R(W)|^T + |b| is a tie: the kernel's fp32 dot product may land on either side of the ReLU kink, and
+    the two sides differ by the whole gradient of that row (like a sampling tie, not a kernel error). The case must
+    have AT MOST 4 such elements -- a condition, so the exemption cannot hide a failure -- and the GPU result is
+    accepted when it matches the oracle under SOME assignment of those masks (<= 16 oracle runs; the oracle's own
+    assignment first). Without ties this is one plain comparison. Returns the tie count."""
+    out, g = run_oracle(None)
+    ties = out["relu_ties"]
+    assert len(ties) <= 4, f"{len(ties)} ReLU tie elements (at most 4 allowed): {ties[:8]}"
+    if not ties:
+        check(out, g)
+        return 0
+    own = tuple(bool(out["relu_pre"][key][0][idx] > 0) for key, idx, _ in ties)
+    first = None
+    for flips in itertools.product((False, True), repeat=len(ties)):
+        ov = {}
+        for (key, idx, _), own_side, fl in zip(ties, own, flips):
+            ov.setdefault(key, {})[idx] = own_side != fl
+        if any(flips):
+            out, g = run_oracle(ov)
+        try:
+            check(out, g)
+            return len(ties)
+        except AssertionError as e:
+            first = first or e
+    raise first
+
+
+def _run_module(Q, K, V, mask, u, dX, dsp, params, k, training=False, bf16=False):
     from csa_amd.module.sbm_attn import SBMAttention
     B, H, N, d = Q.shape
-    m = SBMAttention({"attention_dropout": 0.2, "head_dim": d, "num_head": H, "num_clusters": [k]}, 0)
+    m = SBMAttention({"attention_dropout": 0.2, "head_dim": d, "num_head": H, "num_clusters": [k],
+                      "attn_precision": "bf16" if bf16 else "fp32"}, 0)
     m.load_state_dict(params, strict=False)
     m = m.cuda().train(training)
     q, kk, v = (t.cuda().requires_grad_(True) for t in (Q, K, V))
@@ -533,29 +568,62 @@ def test_sbm_dead_key_tiles_match_oracle(shape):
     positions included, sbm_attn.py:64), the sparsity, X, dQ / dK / dV and every parameter gradient -- dC and the MLP
     weights take the STE term of the dead tiles' edges -- against the fp64 closed form; two runs bitwise identical."""
     B, H, N, d, k = shape
-    # (seed 97 + N at d = 96, k = 16 put one projection-MLP activation of an unpadded AST within fp32 rounding of
-    # the ReLU kink: its K row's dK differs from the fp64 oracle by 1e-3 relative in every build, the round-start one
-    # included -- a tie like the sampling ties above, not a dead-tile effect; profiles/r06_dead_tile_diag.txt)
-    Q, K, V, _, u, dX, dsp, params = _rand_case(B, H, N, d, k, seed=101 + N)
+    # (at d = 96, k = 16 two second-layer activations of the K MLP lie within fp32 rounding of the ReLU kink, the nearer
+    # at 0.14 * 2^-24 of its error bound: the ReLU-tie rule above covers them)
+    Q, K, V, _, u, dX, dsp, params = _rand_case(B, H, N, d, k, seed=97 + N)
     mask = _dead_tile_masks(B, N)
     r1 = _run_module(Q, K, V, mask, u, dX, dsp, params, k)
     r2 = _run_module(Q, K, V, mask, u, dX, dsp, params, k)
     for a, b in zip(r1[:6], r2[:6]):
         assert torch.equal(a, b)
     X, sp, graph, dQ, dK, dV, grads = r1
-    ref, rg = closed_form.sbm_fwd_bwd(Q, K, V, mask, params, u, k, dX, dsp, graph_override=graph)
-    near = (torch.abs(u - ref["expA"].clamp(0.01, 0.99)) < 1e-6)
-    assert bool(torch.all(near[graph != ref["graph"].float()])), "graph flips away from fp32 ties"
     assert float(graph[:, :, :, 64:].sum()) > 0  # sampled edges at padded keys are kept (and counted)
-    np.testing.assert_allclose(sp.numpy(), ref["sparsity"].numpy(), rtol=1e-6)
     live = mask.sum(1) < N  # rows with no valid key are 0/0 in the reference (NaN) -- compared where finite
-    np.testing.assert_allclose(X[live].numpy(), ref["X"][live].numpy(), rtol=RTOL, atol=ATOL)
-    for name, t, key in (("dQ", dQ, "Q"), ("dK", dK, "K"), ("dV", dV, "V")):
-        np.testing.assert_allclose(t[live].numpy(), rg[key][live].numpy(), rtol=RTOL, atol=ATOL, err_msg=name)
     assert torch.all(dK[~live] == 0) and torch.all(dV[~live] == 0)
-    if bool(live.all()):
-        for pn, gv in grads.items():
-            np.testing.assert_allclose(gv.numpy(), rg[pn].numpy(), rtol=RTOL, atol=ATOL, err_msg=pn)
+
+    def check(ref, rg):
+        near = (torch.abs(u - ref["expA"].clamp(0.01, 0.99)) < 1e-6)
+        assert bool(torch.all(near[graph != ref["graph"].float()])), "graph flips away from fp32 ties"
+        np.testing.assert_allclose(sp.numpy(), ref["sparsity"].numpy(), rtol=1e-6)
+        np.testing.assert_allclose(X[live].numpy(), ref["X"][live].numpy(), rtol=RTOL, atol=ATOL)
+        for name, t, key in (("dQ", dQ, "Q"), ("dV", dV, "V")):
+            np.testing.assert_allclose(t[live].numpy(), rg[key][live].numpy(), rtol=RTOL, atol=ATOL, err_msg=name)
+        err = (dK.double() - rg["K"]).abs()
+        ok = err <= RTOL * rg["K"].abs() + ATOL + cancel
+        assert bool(ok[live].all()), f"dK: {int((~ok[live]).sum())} elements, max error {float(err[live].max()):.3g}"
+        if bool(live.all()):
+            for pn, gv in grads.items():
+                np.testing.assert_allclose(gv.numpy(), rg[pn].numpy(), rtol=RTOL, atol=ATOL, err_msg=pn)
+
+    # One row gets more than 1e-4 / 1e-5: the dK row of the only valid key j0 of an AST with ONE valid key. Every query
+    # of that AST has attn = 1 on j0, so dM = (dX . V_j0 - gamma) / D cancels exactly: the attention part of that dK
+    # row is 0 in exact arithmetic (asserted: what the fp64 oracle leaves there is the MLP / STE part, < 1e-8), and in
+    # ANY fp32 implementation it is the fp32 rounding of dX . V (~1e-6 per query) summed over the N queries, which
+    # reaches the 1e-5 atol at N = 2080 (9.9e-6 in the fp32 oracle; 1.8e-6 to 4.1e-6 at N <= 300). Where the
+    # fp32-arithmetic oracle's own error on that row is itself above half the atol, the row is allowed twice that error
+    # (the fp32 oracle run on the fp64 run's graph AND ReLU masks, so no tie can leak in), asserted below 3e-5: at
+    # N = 2080 only. Every other row of dQ / dK / dV, and this row at the shorter shapes, stays at 1e-4 / 1e-5.
+    cancel = torch.zeros(B, H, N, 1, dtype=torch.float64)
+    o64, r64 = closed_form.sbm_fwd_bwd(Q, K, V, mask, params, u, k, dX, dsp, graph_override=graph)
+    for b in range(B):
+        valid = (mask[b] == 0).nonzero().flatten()
+        if len(valid) != 1:
+            continue
+        j0 = int(valid[0])
+        _, r32 = closed_form.sbm_fwd_bwd(Q[b:b + 1], K[b:b + 1], V[b:b + 1], mask[b:b + 1], params, u[b:b + 1], k,
+                                         dX[b:b + 1], dsp / B, graph_override=graph[b:b + 1], dtype=torch.float32,
+                                         relu_override={kk: m[b:b + 1] for kk, m in o64["relu_masks"].items()})
+        assert float(r64["K"][b, :, j0].abs().max()) < 1e-8
+        own = (r32["K"][0, :, j0].double() - r64["K"][b, :, j0]).abs().amax(-1, keepdim=True)
+        cancel[b, :, j0] = torch.where(own > 0.5 * ATOL, 2 * own, torch.zeros_like(own))
+    assert float(cancel.max()) < 3e-5 and int((cancel > 0).sum()) <= H and (N > 300 or not bool(cancel.any()))
+
+    def run_oracle(ov):
+        out, rg = closed_form.sbm_fwd_bwd(Q, K, V, mask, params, u, k, dX, dsp, graph_override=graph, relu_override=ov)
+        out["graph"] = (u < out["expA"].clamp(0.01, 0.99)).double()  # the oracle's own sampling, for the tie check
+        return out, rg
+
+    _match_oracle_up_to_relu_ties(run_oracle, check)
 
 
 @pytest.mark.skipif(not has_gpu(), reason="needs GPU")
