@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSA_HIP_LIB", os.path.join(_HERE, "lib", "libcsa_hip.so"))
 
-CSA_ABI_VERSION = 9
+CSA_ABI_VERSION = 10
 CSA_FLAG_DENSE = 1
 CSA_FLAG_FWD_ONLY = 2
 CSA_FLAG_BF16_WS = 4  # ABI v8: bf16-mode backward workspace (no fp32 tile handoff)
@@ -128,6 +128,20 @@ class AdamwArgs(ctypes.Structure):
 ADAMW_CHUNK = 4096  # CSA_ADAMW_CHUNK
 
 
+class DecodeAttnArgs(ctypes.Structure):  # ABI v10
+    _fields_ = [
+        ("B", i64), ("H", i64), ("hd", i64), ("len", i64), ("t", i64),
+        ("q", vp), ("q_sb", i64), ("q_sh", i64),
+        ("K", vp), ("k_sb", i64), ("k_sh", i64), ("k_sn", i64),
+        ("V", vp), ("v_sb", i64), ("v_sh", i64), ("v_sn", i64),
+        ("k_new", vp), ("kn_sb", i64), ("kn_sh", i64),
+        ("v_new", vp), ("vn_sb", i64), ("vn_sh", i64),
+        ("mask", vp), ("mask_sb", i64), ("mask_sh", i64),
+        ("scale", f32),
+        ("out", vp),
+    ]
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -207,6 +221,12 @@ def lib():
     L.csa_collate_relations.argtypes = [vp, vp, i64, vp, vp, vp, vp, ctypes.c_int]
     L.csa_adamw_step.restype = ctypes.c_int
     L.csa_adamw_step.argtypes = [ctypes.POINTER(AdamwArgs), vp]
+    L.csa_decode_attn_supported.restype = ctypes.c_int
+    L.csa_decode_attn_supported.argtypes = [i64]
+    L.csa_decode_attn.restype = ctypes.c_int
+    L.csa_decode_attn.argtypes = [ctypes.POINTER(DecodeAttnArgs), vp]
+    L.csa_argmax_rows.restype = ctypes.c_int
+    L.csa_argmax_rows.argtypes = [vp, i64, i64, vp, i64, vp, i64, i64, vp, vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -234,4 +254,5 @@ EXPORTED_SYMBOLS = (
     "csa_layernorm_supported", "csa_layernorm_bwd_workspace_bytes", "csa_layernorm_fwd", "csa_layernorm_bwd",
     "csa_residual_dropout_fwd", "csa_residual_dropout_bwd", "csa_gelu_dropout_fwd", "csa_gelu_dropout_bwd",
     "csa_collate_relations",
+    "csa_decode_attn_supported", "csa_decode_attn", "csa_argmax_rows",
 )

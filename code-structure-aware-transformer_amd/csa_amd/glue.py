@@ -249,6 +249,37 @@ class MultiheadAttention(nn.MultiheadAttention):
         o = o.transpose(1, 2).reshape(B, T, E)
         return linear(o, self.out_proj.weight, self.out_proj.bias).transpose(0, 1), None
 
+    # ---- KV-cached decoding (inference): one query position per call, csa_amd/decode_ops.py ----
+
+    def project_memory(self, memory):
+        """The cross-attention K/V projection of a batch-first memory (B, S, E) as (B, S, 2, H, hd): what
+        forward() recomputes from `key` at every call, computed once per batch for step()."""
+        B, S, E = memory.shape
+        w_kv, b_kv = self.in_proj_weight[E:], self.in_proj_bias[E:]
+        return F.linear(memory, w_kv, b_kv).view(B, S, 2, self.num_heads, E // self.num_heads)
+
+    def step(self, x, k_cache=None, v_cache=None, t=None, memory_kv=None, key_mask=None):
+        """forward() for the single query position x (B, 1, E), eval mode (no dropout), need_weights=False.
+
+        Self-attention (memory_kv None): the packed QKV projection of x; this position's key / value rows are
+        appended to k_cache / v_cache (B, H, Tmax, hd) at row t and the query attends to rows 0..t, which is
+        the causal row t of forward(). Cross-attention: the q projection alone against memory_kv =
+        project_memory(memory). key_mask: (B, >= keys) or (B, H, >= keys) uint8, non-zero = masked key (a
+        key-padding mask). Inference only: the projections are plain F.linear (hipBLASLt), no autograd glue."""
+        from .decode_ops import decode_attention
+        B, _, E = x.shape
+        H = self.num_heads
+        hd = E // H
+        if memory_kv is None:
+            qkv = F.linear(x, self.in_proj_weight, self.in_proj_bias).view(B, 3, H, hd)
+            q, k_new, v_new = qkv.unbind(1)
+            o = decode_attention(q, k_cache, v_cache, key_mask=key_mask, k_new=k_new, v_new=v_new, t=t)
+        else:
+            q = F.linear(x, self.in_proj_weight[:E], self.in_proj_bias[:E]).view(B, H, hd)
+            k, v = (u.transpose(1, 2) for u in memory_kv.unbind(2))  # (B, H, S, hd) views
+            o = decode_attention(q, k, v, key_mask=key_mask)
+        return F.linear(o, self.out_proj.weight, self.out_proj.bias).view(B, 1, E)
+
 
 class _SplitHeads3(torch.autograd.Function):
     @staticmethod

@@ -67,6 +67,13 @@ class Embeddings(nn.Module):
             e = self.pos_emb(e)
         return self.dropout(self.norm(e))
 
+    def step(self, x, t):
+        """forward() for the single position t: tokens x (B, 1) -> the row forward() gives at index t."""
+        e = self.word_embeddings(x)
+        if self.pos_emb is not None:
+            e = e + self.pos_emb.pe[:, t:t + 1]
+        return self.dropout(self.norm(e))
+
 
 class FeedForward(nn.Module):
     def __init__(self, d_model, dim_feed_forward, dropout=0.1):
@@ -215,6 +222,36 @@ class DecoderLayer(nn.Module):
         tgt, _ = self.sublayer[2](tgt, self.feed_forward)
         return tgt, w
 
+    def step(self, x, cache, i, t):
+        """forward() in eval mode for the single position t, x (B, 1, E): x + sublayer(norm(x)) three times
+        against layer i's slots of a DecodeCache."""
+        sl = self.sublayer
+        x = x + self.self_attn.step(sl[0].norm(x), cache.self_k[i], cache.self_v[i], t, key_mask=cache.self_mask)
+        x = x + self.multihead_attn.step(sl[1].norm(x), memory_kv=cache.memory_kv[i], key_mask=cache.memory_mask)
+        return x + self.feed_forward(sl[2].norm(x))[0]
+
+
+class DecodeCache:
+    """What incremental decoding keeps between steps, owned by the caller (BaseDecoder.make_cache):
+    self_k / self_v  per layer (B, H, max_len, hd): the self-attention keys / values of positions decoded so far;
+    memory_kv        per layer (B, S, 2, H, hd): the cross-attention projection of the encoder memory;
+    memory_mask      (B, S) uint8 source key-padding mask (non-zero = PAD) or None;
+    pad              (B, max_len) uint8: pad[:, j] != 0 where target token j is PAD. The caller sets column t before
+                     step t (column 0, BOS, is 0); it is the key-padding half of make_std_mask, the causal half
+                     being the cache length itself.
+    head_pad         None, or (B, H, max_len) uint8: the per-head key mask of the reference's decode()
+                     (base_seq2seq.py:99-114). It hands nn.MultiheadAttention `tgt_mask.repeat(num_heads, 1, 1)`,
+                     which that module reads as (B, H, T, T): head h of sample b sees the PAD columns of sample
+                     (b * H + h) % B. BaseDecoder.step copies column t of pad into this layout before step t."""
+
+    def __init__(self, self_k, self_v, memory_kv, memory_mask, pad, head_pad=None):
+        self.self_k, self.self_v, self.memory_kv = self_k, self_v, memory_kv
+        self.memory_mask, self.pad, self.head_pad = memory_mask, pad, head_pad
+
+    @property
+    def self_mask(self):
+        return self.pad if self.head_pad is None else self.head_pad
+
 
 class BaseDecoder(nn.Module):
     def __init__(self, decoder_layer, num_layers, norm=None):
@@ -228,6 +265,29 @@ class BaseDecoder(nn.Module):
         for mod in self.layers:
             out, w = mod(out, memory, tgt_mask=tgt_mask, memory_key_padding_mask=memory_key_padding_mask)
         return (self.norm(out) if self.norm is not None else out), w
+
+    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False):
+        """DecodeCache for a batch-first memory (B, S, E) and up to max_len target positions. repeat_heads: key-pad
+        the heads as forward() does when given make_std_mask(...).repeat(num_heads, 1, 1), the reference's decode();
+        otherwise head h of sample b sees sample b's PAD columns (a (B*H, T, T) mask built by repeat_interleave)."""
+        B, _, E = memory.shape
+        H = self.layers[0].self_attn.num_heads
+        kv = [torch.zeros(2, B, H, max_len, E // H, device=memory.device, dtype=memory.dtype) for _ in self.layers]
+        mm = None if memory_key_padding_mask is None else memory_key_padding_mask.to(torch.uint8).contiguous()
+        pad = torch.zeros(B, max_len, dtype=torch.uint8, device=memory.device)
+        head_pad = torch.zeros(B, H, max_len, dtype=torch.uint8, device=memory.device) if repeat_heads else None
+        return DecodeCache([c[0] for c in kv], [c[1] for c in kv],
+                           [mod.multihead_attn.project_memory(memory) for mod in self.layers], mm, pad, head_pad)
+
+    def step(self, x, cache, t):
+        """forward() in eval mode for the single target position t: x (B, 1, E) batch-first -> (B, 1, E), equal to
+        row t of forward() over positions 0..t (the decoder is causal and cache.pad carries the PAD keys)."""
+        if cache.head_pad is not None:  # rows r = h' * B + b' of the (B*H) layout hold pad[b'] (mask.repeat(H, 1, 1))
+            B, H, _ = cache.head_pad.shape
+            cache.head_pad.view(H, B, -1)[:, :, t] = cache.pad[:, t]
+        for i, mod in enumerate(self.layers):
+            x = mod.step(x, cache, i, t)
+        return self.norm(x) if self.norm is not None else x
 
 
 class Generator(nn.Module):
@@ -351,6 +411,43 @@ class GreedyGenerator(nn.Module):
             next_word = torch.max(out, dim=1)[1]
             ys = torch.cat([ys, next_word.unsqueeze(1)], dim=1)
         return ys[:, 1:]
+
+
+class CachedGreedyGenerator(GreedyGenerator):
+    """GreedyGenerator with a key/value cache: the same tokens from one decoder pass per NEW position.
+
+    The decoder is causal and the key-padding mask of positions <= j never changes as ys grows, so step t needs only
+    position t: its embedding, BaseDecoder.step against the cached self-attention keys / values and the once-projected
+    encoder memory (csa_decode_attn), the Generator's linear on the B last rows, and the row argmax written into
+    ys[:, t+1] with the next step's PAD byte (csa_argmax_rows). Eval-mode log(softmax(z)) is monotone in z, so the
+    argmax of the logits is the reference's torch.max(out, 1)[1] and the softmax is skipped unless return_logp asks for
+    the (max_tgt_len-1, B, V) last-position log-probabilities. All max_tgt_len-1 steps always run (no early stop at
+    EOS), as in the reference. In training mode this defers to GreedyGenerator."""
+
+    def forward(self, data, return_logp=False):
+        m = self.model
+        if m.training:
+            ys = super().forward(data)
+            return (ys, None) if return_logp else ys
+        from .decode_ops import argmax_rows
+        from .gen_ops import gen_log_softmax
+        with torch.no_grad():
+            m.process_data(data)
+            enc, _, _, _, _ = m.encode(data)
+            B, T = enc.size(0), self.max_tgt_len
+            cache = m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True)  # as CSATrans.decode masks
+            ys = torch.zeros(B, T, dtype=torch.long, device=enc.device)
+            ys[:, 0] = self.start_pos
+            logps = []
+            for t in range(T - 1):
+                x = m.tgt_embedding.step(ys[:, t:t + 1], t)
+                dec = m.decoder.step(x, cache, t)
+                logits = m.generator.linear(dec[:, 0])
+                argmax_rows(logits, out=ys[:, t + 1], is_pad=cache.pad[:, t + 1], pad_id=PAD)
+                if return_logp:
+                    logps.append(gen_log_softmax(logits, 0.0))
+            out = ys[:, 1:]
+            return (out, torch.stack(logps)) if return_logp else out
 
 
 class _GatherTargets(torch.autograd.Function):

@@ -1,0 +1,293 @@
+// Incremental (KV-cached) greedy decoding on gfx950: the two kernels of one decode step that are not a GEMM.
+//
+//   k_decode_attn   softmax(q K^T * scale + key mask) V for ONE query row per (batch, head): the decoder's
+//                   self-attention against its K/V cache (optionally appending this step's key/value row) and
+//                   its cross-attention against the projected encoder memory, both through strides.
+//   k_argmax_rows   row argmax of the last-position logits, written straight into ys[:, t+1] together with
+//                   the next step's PAD key-mask byte.
+//
+// M = 1, so there is no matrix product to feed an MFMA: both kernels are bound by memory latency (a few
+// hundred KB to a few tens of MB per launch) and are written for wave64 with 16-byte global loads.
+//
+// k_decode_attn: one wave per (b, h), DEC_WAVES waves per workgroup. Keys are walked in chunks of 64:
+//   scores   lane l owns key 64 c + l and reads its whole row as float4 (q is broadcast from LDS);
+//   softmax  online over chunks (running max m, running sum l). A chunk whose 64 keys are all masked while
+//            m is still -inf is skipped outright, and the rescale factor of the first live chunk is 0 by
+//            construction, so exp(-inf - (-inf)) is never evaluated; tail lanes (key >= len) score -inf and
+//            their probability is an exact 0;
+//   P.V      the chunk's probabilities sit in LDS; lane l owns the float4 column group l % (hd/4) and the key
+//            group l / (hd/4), so a row of V is read by hd/4 adjacent lanes (coalesced). The key groups are
+//            summed through LDS in a fixed order.
+// Every sum has a fixed order: results are bitwise reproducible.
+// A row whose keys are all masked ends with l = 0 and gives 0/0 = NaN (as SDPA does for an all -inf mask).
+// Append mode: the wave copies k_new / v_new into cache row t and reads key t from k_new / v_new themselves,
+// never from the row it has just stored (no read-after-write through global memory).
+#include "csa_common.hpp"
+#include "../../include/csa_hip.h"
+
+#include <math.h>
+
+using namespace csa;
+
+namespace {
+
+constexpr int DEC_WAVES = 4;      // (b, h) pairs per workgroup
+constexpr int DEC_MAX_HD = 128;
+constexpr int PV_U = 8;           // V rows a lane keeps in flight in the P.V phase
+constexpr int ARG_T = 256;
+
+struct DecArgs {
+  int BH, H, hd, len, t;  // t < 0: no append
+  const float* q; int64_t q_sb, q_sh;
+  float* K; int64_t k_sb, k_sh, k_sn;
+  float* V; int64_t v_sb, v_sh, v_sn;
+  const float* k_new; int64_t kn_sb, kn_sh;
+  const float* v_new; int64_t vn_sb, vn_sh;
+  const uint8_t* mask; int64_t mask_sb, mask_sh;
+  float scale;
+  float* out;
+};
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a) {
+  __shared__ f32x4 qs[DEC_WAVES][DEC_MAX_HD / 4];
+  __shared__ float ps[DEC_WAVES][64];
+  __shared__ f32x4 red[DEC_WAVES][64];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int bh_raw = blockIdx.x * DEC_WAVES + w;
+  // the workgroup's barriers need every wave: a wave past the last (b, h) redoes the last pair and stores nothing
+  const bool valid = bh_raw < a.BH;
+  const int bh = valid ? bh_raw : a.BH - 1;
+  const int b = bh / a.H, h = bh - b * a.H;
+  const int DC = a.hd >> 2;   // float4 column groups per row (<= 32)
+  const int KG = 64 / DC;     // key groups of the P.V phase (>= 2)
+  const bool append = a.t >= 0;
+
+  const float* qrow = a.q + b * a.q_sb + h * a.q_sh;
+  float* Kb = a.K + b * a.k_sb + h * a.k_sh;
+  float* Vb = a.V + b * a.v_sb + h * a.v_sh;
+  const float* knew = append ? a.k_new + b * a.kn_sb + h * a.kn_sh : nullptr;
+  const float* vnew = append ? a.v_new + b * a.vn_sb + h * a.vn_sh : nullptr;
+  const uint8_t* mrow = a.mask ? a.mask + b * a.mask_sb + h * a.mask_sh : nullptr;
+
+  if (lane < DC) {
+    qs[w][lane] = reinterpret_cast<const f32x4*>(qrow)[lane];
+    if (append && valid) {  // this step's key / value row -> cache row t (rows above t are never touched)
+      reinterpret_cast<f32x4*>(Kb + (int64_t)a.t * a.k_sn)[lane] = reinterpret_cast<const f32x4*>(knew)[lane];
+      reinterpret_cast<f32x4*>(Vb + (int64_t)a.t * a.v_sn)[lane] = reinterpret_cast<const f32x4*>(vnew)[lane];
+    }
+  }
+  __syncthreads();
+
+  const int dc = lane % DC, kg = lane / DC;
+  const bool pv_lane = kg < KG;  // 64 % DC lanes idle when hd/4 does not divide 64
+  float m = -INFINITY, l = 0.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+
+  for (int j0 = 0; j0 < a.len; j0 += 64) {
+    // ---- scores of keys j0 .. j0 + 63 (lane = key) ----
+    const int j = j0 + lane;
+    const bool in = j < a.len;
+    const int jc = in ? j : a.len - 1;  // always a readable row; the value is dropped below
+    const float* krow = (append && jc == a.t) ? knew : Kb + (int64_t)jc * a.k_sn;
+    float s = 0.f;
+#pragma unroll 8
+    for (int c = 0; c < DC; ++c) {
+      const f32x4 kv = reinterpret_cast<const f32x4*>(krow)[c];
+      const f32x4 qv = qs[w][c];
+      s += qv[0] * kv[0];
+      s += qv[1] * kv[1];
+      s += qv[2] * kv[2];
+      s += qv[3] * kv[3];
+    }
+    s *= a.scale;
+    const bool masked = mrow ? mrow[jc] != 0 : false;
+    s = (in && !masked) ? s : -INFINITY;
+
+    // ---- online softmax ----
+    const float mn = fmaxf(m, wave_max(s));  // wave-uniform
+    // mn == -inf: nothing live yet (this chunk included): p = 0 everywhere, state unchanged
+    const bool live = mn > -INFINITY;
+    const float alpha = (m > -INFINITY) ? expf(m - mn) : 0.f;  // first live chunk: acc and l are 0 anyway
+    const float p = (live && s > -INFINITY) ? expf(s - mn) : 0.f;
+    __syncthreads();  // the previous chunk's P.V reads of ps are done
+    ps[w][lane] = p;
+    __syncthreads();
+    if (live) {
+      l = l * alpha + wave_sum(p);
+      m = mn;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] *= alpha;
+      // ---- acc += P V over this chunk's keys (lane = key group x float4 column group) ----
+      const int nk = (a.len - j0 < 64) ? a.len - j0 : 64;
+      if (pv_lane) {
+        // PV_U rows in flight per lane: the loads of a group are independent (issued together, row index clamped
+        // to a real row and the value zeroed past the chunk), the FMAs keep the key order
+        for (int jj = kg; jj < nk; jj += PV_U * KG) {
+          f32x4 vv[PV_U];
+          float pj[PV_U];
+#pragma unroll
+          for (int u = 0; u < PV_U; ++u) {
+            const int ju = jj + u * KG;
+            const bool ok = ju < nk;
+            const int jl = ok ? ju : jj;
+            const int jk = j0 + jl;
+            const float* vrow = (append && jk == a.t) ? vnew : Vb + (int64_t)jk * a.v_sn;
+            const f32x4 x = reinterpret_cast<const f32x4*>(vrow)[dc];
+            pj[u] = ok ? ps[w][jl] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) vv[u][e] = ok ? x[e] : 0.f;
+          }
+#pragma unroll
+          for (int u = 0; u < PV_U; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] += pj[u] * vv[u][e];
+        }
+      }
+    }
+  }
+
+  // ---- sum the key groups in a fixed order, normalise, store ----
+  red[w][lane] = acc;
+  __syncthreads();
+  if (lane < DC && valid) {
+    f32x4 o = red[w][lane];
+    for (int g = 1; g < KG; ++g) {
+      const f32x4 r = red[w][g * DC + lane];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] += r[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = o[e] / l;  // all keys masked: 0 / 0 = NaN
+    reinterpret_cast<f32x4*>(a.out + ((int64_t)b * a.H + h) * a.hd)[lane] = o;
+  }
+}
+
+// ---- row argmax: lowest index among the maxima; an all -inf row gives index 0 ----
+__device__ __forceinline__ void arg_merge(float& v, int64_t& i, float vo, int64_t io) {
+  if (vo > v || (vo == v && io < i)) { v = vo; i = io; }
+}
+
+__global__ __launch_bounds__(ARG_T) void k_argmax_rows(const float* __restrict__ x, int64_t V, int64_t* __restrict__ idx,
+                                                      int64_t idx_stride, uint8_t* __restrict__ is_pad,
+                                                      int64_t pad_stride, int64_t pad_id, float* __restrict__ maxval) {
+  __shared__ float rv[ARG_T / 64];
+  __shared__ int64_t ri[ARG_T / 64];
+  const int64_t row = blockIdx.x;
+  const float* xr = x + row * V;
+  // a thread walks its columns in increasing order with a strict >, so it keeps the lowest index of its maximum;
+  // i = V marks "nothing above -inf seen" and loses every tie against a real index
+  float v = -INFINITY;
+  int64_t i = V;
+  const bool vec = (V % 4 == 0) && (((uintptr_t)x) & 15) == 0;
+  if (vec) {
+    for (int64_t c = 4 * (int64_t)threadIdx.x; c < V; c += 4 * ARG_T) {
+      const f32x4 q = *reinterpret_cast<const f32x4*>(xr + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (q[e] > v) { v = q[e]; i = c + e; }
+    }
+  } else {
+    for (int64_t c = threadIdx.x; c < V; c += ARG_T) {
+      const float q = xr[c];
+      if (q > v) { v = q; i = c; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float vo = __shfl_xor(v, o, 64);
+    const int64_t io = __shfl_xor(i, o, 64);
+    arg_merge(v, i, vo, io);
+  }
+  if ((threadIdx.x & 63) == 0) { rv[threadIdx.x >> 6] = v; ri[threadIdx.x >> 6] = i; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < ARG_T / 64; ++k) arg_merge(v, i, rv[k], ri[k]);
+    if (i >= V) i = 0;  // all -inf (or NaN): index 0, always inside [0, V)
+    idx[row * idx_stride] = i;
+    if (is_pad) is_pad[row * pad_stride] = (i == pad_id) ? 1 : 0;
+    if (maxval) maxval[row] = v;
+  }
+}
+
+csa_status dfail(csa_status s, const char* m) {
+  csa::set_error("%s", m);
+  return s;
+}
+
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+inline bool m4(int64_t s) { return s % 4 == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int csa_decode_attn_supported(int64_t hd) { return (hd >= 4 && hd <= DEC_MAX_HD && hd % 4 == 0) ? 1 : 0; }
+
+csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream) {
+  if (!a) return dfail(CSA_INVALID_ARG, "csa_decode_attn: null args");
+  if (a->B < 0 || a->H < 1 || a->len < 1 || a->B * a->H > 0x7fffffff || a->len > 0x7fffffff)
+    return dfail(CSA_INVALID_ARG, "csa_decode_attn: B, H, len must be positive (len >= 1)");
+  if (!csa_decode_attn_supported(a->hd))
+    return dfail(CSA_UNSUPPORTED_SHAPE, "csa_decode_attn: hd must be a multiple of 4 in [4, 128]");
+  const bool append = a->k_new || a->v_new;
+  if (append && (!a->k_new || !a->v_new)) return dfail(CSA_INVALID_ARG, "csa_decode_attn: k_new and v_new go together");
+  if (append && (a->t < 0 || a->t + 1 != a->len))
+    return dfail(CSA_INVALID_ARG, "csa_decode_attn: append mode needs len == t + 1");
+  if (a->B == 0) return CSA_OK;
+  if (!a->q || !a->K || !a->V || !a->out) return dfail(CSA_INVALID_ARG, "csa_decode_attn: null pointer");
+  if (!al16(a->q) || !al16(a->K) || !al16(a->V) || !al16(a->out) || !al16(a->k_new) || !al16(a->v_new) ||
+      !m4(a->q_sb) || !m4(a->q_sh) || !m4(a->k_sb) || !m4(a->k_sh) || !m4(a->k_sn) || !m4(a->v_sb) || !m4(a->v_sh) ||
+      !m4(a->v_sn) || (append && (!m4(a->kn_sb) || !m4(a->kn_sh) || !m4(a->vn_sb) || !m4(a->vn_sh))))
+    return dfail(CSA_INVALID_ARG, "csa_decode_attn: pointers must be 16-byte aligned and strides multiples of 4 elements");
+  DecArgs d;
+  d.BH = (int)(a->B * a->H); d.H = (int)a->H; d.hd = (int)a->hd; d.len = (int)a->len; d.t = append ? (int)a->t : -1;
+  d.q = a->q; d.q_sb = a->q_sb; d.q_sh = a->q_sh;
+  d.K = a->K; d.k_sb = a->k_sb; d.k_sh = a->k_sh; d.k_sn = a->k_sn;
+  d.V = a->V; d.v_sb = a->v_sb; d.v_sh = a->v_sh; d.v_sn = a->v_sn;
+  d.k_new = a->k_new; d.kn_sb = a->kn_sb; d.kn_sh = a->kn_sh;
+  d.v_new = a->v_new; d.vn_sb = a->vn_sb; d.vn_sh = a->vn_sh;
+  d.mask = a->mask; d.mask_sb = a->mask_sb; d.mask_sh = a->mask_sh;
+  d.scale = a->scale;
+  d.out = a->out;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  hipLaunchKernelGGL(k_decode_attn, dim3((unsigned)((d.BH + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, st, d);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_decode_attn: %s", hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+csa_status csa_argmax_rows(const float* x, int64_t rows, int64_t V, int64_t* idx, int64_t idx_stride, uint8_t* is_pad,
+                           int64_t pad_stride, int64_t pad_id, float* maxval, void* stream) {
+  if (rows < 0 || V < 1 || rows > 0x7fffffff) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: bad rows / V");
+  if (!x || !idx) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: null pointer");
+  if ((((uintptr_t)x) & 3) || (((uintptr_t)idx) & 7)) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: misaligned pointer");
+  if (rows == 0) return CSA_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  hipLaunchKernelGGL(k_argmax_rows, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, idx, idx_stride, is_pad, pad_stride,
+                     pad_id, maxval);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_argmax_rows: %s", hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@
  *   csa_bias_grad      Linear bias gradient (column sums of dY) of the encoder/decoder glue
  *   csa_layernorm_fwd/_bwd  nn.LayerNorm of the encoder glue (module/components.py SublayerConnection)
  *   csa_ast_relations  my_ast.py:198-273 + dataset/base_data_set.py:33-36 (host C++, no GPU)
+ *   csa_decode_attn / csa_argmax_rows  module/base_seq2seq.py:117-145 GreedyGenerator, one KV-cached decode step
  *
  * Conventions (all entry points):
  *   - fp32 data; device pointers; sizes and strides are int64 ELEMENT counts; the last
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define CSA_ABI_VERSION 9
+#define CSA_ABI_VERSION 10
 
 typedef enum csa_status {
   CSA_OK = 0,
@@ -266,6 +267,38 @@ csa_status csa_gen_logsoftmax_fwd(const float* logits, float* logp, int64_t rows
                                   uint64_t seed, uint64_t offset, void* stream);
 csa_status csa_gen_logsoftmax_bwd(const float* dlogp, const float* logp, float* dlogits, int64_t rows, int64_t V,
                                   float dropout, uint64_t seed, uint64_t offset, void* stream);
+
+/* ---- ABI v10: KV-cached greedy decoding (module/base_seq2seq.py:117-145 GreedyGenerator, one token per step) ----
+ * csa_decode_attn: out[b, h*hd : (h+1)*hd] = softmax(scale * q[b,h] . K[b,h,j] over keys j < len, masked keys
+ * at -inf) . V[b,h,j], one query row per (b, h), fp32 throughout. hd % 4 == 0 and hd <= 128
+ * (csa_decode_attn_supported); any len >= 1. q is (B,H,hd) and K / V are (B,H,>=len,hd) through their element
+ * strides, hd contiguous: the same call reads the decoder's self-attention cache and the two planes of a
+ * (B,S,2,H,hd) cross-attention memory projection. mask: optional (B,>=len) bytes, non-zero = masked key (a head
+ * stride mask_sh != 0 reads a per-head (B,H,>=len) mask instead); a row whose keys are all masked gives NaN (0/0,
+ * as SDPA with an all -inf mask), never a fault.
+ * Append mode (k_new and v_new both set; len == t + 1): this step's key / value rows (B,H,hd) are stored to
+ * cache row t of K / V and used as key t from k_new / v_new themselves; cache rows above t are not touched.
+ * Every pointer 16-byte aligned, every stride a multiple of 4 elements. Deterministic (fixed summation order). */
+typedef struct csa_decode_attn_args {
+  int64_t B, H, hd, len, t;                   /* t: append position, read only in append mode */
+  const float* q; int64_t q_sb, q_sh;         /* (B,H,hd) */
+  float* K; int64_t k_sb, k_sh, k_sn;         /* (B,H,>=len,hd); written (row t) only in append mode */
+  float* V; int64_t v_sb, v_sh, v_sn;
+  const float* k_new; int64_t kn_sb, kn_sh;   /* (B,H,hd) or NULL */
+  const float* v_new; int64_t vn_sb, vn_sh;   /* (B,H,hd) or NULL */
+  const uint8_t* mask; int64_t mask_sb, mask_sh; /* (B,>=len) with mask_sh = 0, (B,H,>=len), or NULL */
+  float scale;                                /* hd^-0.5 */
+  float* out;                                 /* (B, H*hd) contiguous */
+} csa_decode_attn_args;
+
+int csa_decode_attn_supported(int64_t hd);
+csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream);
+/* Row argmax of x (rows, V) contiguous fp32: idx[r * idx_stride] = the LOWEST index of row r's maximum (strict >
+ * from index 0; an all -inf row gives 0; always in [0, V)), e.g. ys[:, t+1] of an int64 (B, T) token buffer in
+ * place. Optional: is_pad[r * pad_stride] = (index == pad_id) as a byte (the next step's key mask), maxval[r] = the
+ * row maximum. The eval-mode Generator's log(softmax(z)) is monotone in z, so this is its torch.max(out, 1)[1]. */
+csa_status csa_argmax_rows(const float* x, int64_t rows, int64_t V, int64_t* idx, int64_t idx_stride, uint8_t* is_pad,
+                           int64_t pad_stride, int64_t pad_id, float* maxval, void* stream);
 
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
