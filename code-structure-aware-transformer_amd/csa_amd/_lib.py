@@ -227,6 +227,12 @@ def lib():
     L.csa_decode_attn.argtypes = [ctypes.POINTER(DecodeAttnArgs), vp]
     L.csa_argmax_rows.restype = ctypes.c_int
     L.csa_argmax_rows.argtypes = [vp, i64, i64, vp, i64, vp, i64, i64, vp, vp]
+    L.csa_decode_attn_step.restype = ctypes.c_int  # v10 additions: the step index read from a device counter
+    L.csa_decode_attn_step.argtypes = [ctypes.POINTER(DecodeAttnArgs), vp, vp]
+    L.csa_decode_embed.restype = ctypes.c_int
+    L.csa_decode_embed.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, f32, vp, i64, vp]
+    L.csa_argmax_rows_step.restype = ctypes.c_int
+    L.csa_argmax_rows_step.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, i64, vp, vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -255,4 +261,5 @@ EXPORTED_SYMBOLS = (
     "csa_residual_dropout_fwd", "csa_residual_dropout_bwd", "csa_gelu_dropout_fwd", "csa_gelu_dropout_bwd",
     "csa_collate_relations",
     "csa_decode_attn_supported", "csa_decode_attn", "csa_argmax_rows",
+    "csa_decode_attn_step", "csa_decode_embed", "csa_argmax_rows_step",
 )

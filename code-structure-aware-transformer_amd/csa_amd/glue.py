@@ -263,7 +263,8 @@ class MultiheadAttention(nn.MultiheadAttention):
 
         Self-attention (memory_kv None): the packed QKV projection of x; this position's key / value rows are
         appended to k_cache / v_cache (B, H, Tmax, hd) at row t and the query attends to rows 0..t, which is
-        the causal row t of forward(). Cross-attention: the q projection alone against memory_kv =
+        the causal row t of forward(); t is an int, or a 1-element int32 device counter that the kernel reads
+        itself (the caches' row count is then the capacity). Cross-attention: the q projection alone against memory_kv =
         project_memory(memory). key_mask: (B, >= keys) or (B, H, >= keys) uint8, non-zero = masked key (a
         key-padding mask). Inference only: the projections are plain F.linear (hipBLASLt), no autograd glue."""
         from .decode_ops import decode_attention

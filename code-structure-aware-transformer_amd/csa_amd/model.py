@@ -68,7 +68,12 @@ class Embeddings(nn.Module):
         return self.dropout(self.norm(e))
 
     def step(self, x, t):
-        """forward() for the single position t: tokens x (B, 1) -> the row forward() gives at index t."""
+        """forward() for the single position t: tokens x (B, 1) -> the row forward() gives at index t.
+        With t a device counter (1-element int32 tensor) x is the whole (B, T) token buffer and the kernel picks
+        column t itself (decode_ops.decode_embed; eval mode only)."""
+        if isinstance(t, torch.Tensor):
+            from .decode_ops import decode_embed
+            return decode_embed(x, t, self).unsqueeze(1)
         e = self.word_embeddings(x)
         if self.pos_emb is not None:
             e = e + self.pos_emb.pe[:, t:t + 1]
@@ -223,8 +228,8 @@ class DecoderLayer(nn.Module):
         return tgt, w
 
     def step(self, x, cache, i, t):
-        """forward() in eval mode for the single position t, x (B, 1, E): x + sublayer(norm(x)) three times
-        against layer i's slots of a DecodeCache."""
+        """forward() in eval mode for the single position t (an int, or the device counter), x (B, 1, E):
+        x + sublayer(norm(x)) three times against layer i's slots of a DecodeCache."""
         sl = self.sublayer
         x = x + self.self_attn.step(sl[0].norm(x), cache.self_k[i], cache.self_v[i], t, key_mask=cache.self_mask)
         x = x + self.multihead_attn.step(sl[1].norm(x), memory_kv=cache.memory_kv[i], key_mask=cache.memory_mask)
@@ -281,8 +286,11 @@ class BaseDecoder(nn.Module):
 
     def step(self, x, cache, t):
         """forward() in eval mode for the single target position t: x (B, 1, E) batch-first -> (B, 1, E), equal to
-        row t of forward() over positions 0..t (the decoder is causal and cache.pad carries the PAD keys)."""
-        if cache.head_pad is not None:  # rows r = h' * B + b' of the (B*H) layout hold pad[b'] (mask.repeat(H, 1, 1))
+        row t of forward() over positions 0..t (the decoder is causal and cache.pad carries the PAD keys).
+        t is an int, or the device counter (1-element int32 tensor) of device-stepped decoding: the attention kernels
+        then read the step themselves, and column t of head_pad has been written by the previous step's
+        argmax_rows(..., t_dev=, head_pad=), so nothing is copied here."""
+        if cache.head_pad is not None and not isinstance(t, torch.Tensor):  # rows r = h' * B + b' of the (B*H) layout hold pad[b'] (mask.repeat(H, 1, 1))
             B, H, _ = cache.head_pad.shape
             cache.head_pad.view(H, B, -1)[:, :, t] = cache.pad[:, t]
         for i, mod in enumerate(self.layers):
@@ -422,7 +430,23 @@ class CachedGreedyGenerator(GreedyGenerator):
     ys[:, t+1] with the next step's PAD byte (csa_argmax_rows). Eval-mode log(softmax(z)) is monotone in z, so the
     argmax of the logits is the reference's torch.max(out, 1)[1] and the softmax is skipped unless return_logp asks for
     the (max_tgt_len-1, B, V) last-position log-probabilities. All max_tgt_len-1 steps always run (no early stop at
-    EOS), as in the reference. In training mode this defers to GreedyGenerator."""
+    EOS), as in the reference. In training mode this defers to GreedyGenerator.
+
+    graph=True (eval mode, CUDA model): the loop above is bound by the host, about 70 small launches per step issued
+    from Python. The step is instead run device-stepped (every kernel reads t from a 4-byte device counter:
+    csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step), captured once per (device, B, S, max_tgt_len,
+    return_logp, parameter addresses) as one torch.cuda.CUDAGraph over static buffers and replayed max_tgt_len - 1
+    times per call; process_data, encode (its Philox key comes from the CPU generator) and the memory projections
+    stay eager. Same ids and log-probabilities, bitwise. `captures` counts the graphs captured."""
+
+    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+
+    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False):
+        super().__init__(model, max_tgt_len, multi_gpu)
+        self.graph = graph
+        self.captures = 0      # graphs captured so far (graph=True on a CUDA model; 0 otherwise)
+        self._graphs = {}      # key -> SimpleNamespace of static buffers and the captured step (insertion-ordered)
+        self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
 
     def forward(self, data, return_logp=False):
         m = self.model
@@ -434,6 +458,8 @@ class CachedGreedyGenerator(GreedyGenerator):
         with torch.no_grad():
             m.process_data(data)
             enc, _, _, _, _ = m.encode(data)
+            if self.graph and enc.is_cuda:
+                return self._forward_graph(data, enc, return_logp)
             B, T = enc.size(0), self.max_tgt_len
             cache = m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True)  # as CSATrans.decode masks
             ys = torch.zeros(B, T, dtype=torch.long, device=enc.device)
@@ -448,6 +474,85 @@ class CachedGreedyGenerator(GreedyGenerator):
                     logps.append(gen_log_softmax(logits, 0.0))
             out = ys[:, 1:]
             return (out, torch.stack(logps)) if return_logp else out
+
+    # ---- graph=True: one captured HIP graph of a device-stepped decode step, replayed max_tgt_len - 1 times ----
+
+    def _step_params(self):
+        m = self.model
+        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
+        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
+
+    def _device_step(self, e, return_logp):
+        """One decode step with every step-dependent index read from e.t_dev on the device: the same launches for
+        every t, so they can be captured once. Ends by advancing the counter, after its last reader."""
+        from .decode_ops import argmax_rows
+        from .gen_ops import gen_log_softmax
+        m = self.model
+        x = m.tgt_embedding.step(e.ys, e.t_dev)
+        dec = m.decoder.step(x, e.cache, e.t_dev)
+        logits = m.generator.linear(dec[:, 0])
+        argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
+        logp = gen_log_softmax(logits, 0.0) if return_logp else None
+        e.t_dev.add_(1)
+        return logp
+
+    def _reset(self, e):
+        """Step 0 of a new batch. The self-attention cache needs no reset: rows above t are never read."""
+        e.ys.zero_()
+        e.ys[:, 0] = self.start_pos
+        e.cache.pad.zero_()
+        e.cache.head_pad.zero_()
+        e.t_dev.zero_()
+
+    def _capture(self, enc, S, return_logp):
+        m = self.model
+        dev, B, T = enc.device, enc.size(0), self.max_tgt_len
+        E, H = enc.size(2), m.decoder.layers[0].self_attn.num_heads
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
+        kv = [z(2, B, H, T, E // H, dtype=enc.dtype) for _ in m.decoder.layers]
+        cache = DecodeCache([c[0] for c in kv], [c[1] for c in kv],
+                            [z(B, S, 2, H, E // H, dtype=enc.dtype) for _ in m.decoder.layers],
+                            z(B, S, dtype=torch.uint8), z(B, T, dtype=torch.uint8), z(B, H, T, dtype=torch.uint8))
+        e = SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None)
+        self._reset(e)
+        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
+        # are then in place and stay outside the capture
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._device_step(e, return_logp)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        e.graph = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
+        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
+            e.logp = self._device_step(e, return_logp)
+        if self._keep_graph:
+            e.graph.instantiate()
+        self.captures += 1
+        return e
+
+    def _forward_graph(self, data, enc, return_logp):
+        m = self.model
+        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
+        # reallocated parameters recapture; weights updated in place are simply read by the next replay
+        key = (enc.device, B, S, T, bool(return_logp), tuple(p.data_ptr() for p in self._step_params()))
+        e = self._graphs.get(key)
+        if e is None:
+            with torch.cuda.device(enc.device):
+                e = self._capture(enc, S, return_logp)
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                del self._graphs[next(iter(self._graphs))]
+            self._graphs[key] = e
+        for kv, mod in zip(e.cache.memory_kv, m.decoder.layers):
+            kv.copy_(mod.multihead_attn.project_memory(enc))
+        e.cache.memory_mask.copy_(data.src_mask)
+        self._reset(e)
+        logps = []
+        for _ in range(T - 1):
+            e.graph.replay()
+            if return_logp:
+                logps.append(e.logp.clone())
+        out = e.ys[:, 1:].clone()
+        return (out, torch.stack(logps)) if return_logp else out
 
 
 class _GatherTargets(torch.autograd.Function):

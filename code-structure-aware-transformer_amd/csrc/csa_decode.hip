@@ -6,6 +6,14 @@
 //   k_argmax_rows   row argmax of the last-position logits, written straight into ys[:, t+1] together with
 //                   the next step's PAD key-mask byte.
 //
+// Device-stepped variants (one captured HIP graph then serves every step of a batch): the step index t is read by
+// the kernel from a 4-byte device counter instead of being baked into the launch.
+//   k_decode_attn       with DecArgs.t_dev set: append at row *t_dev, t + 1 keys; the grid never depended on the length
+//   k_argmax_rows_step  k_argmax_rows writing column *t_dev + 1 of ys / pad and of the per-head (H, B, T) key mask
+//   k_decode_embed      LayerNorm(W[ys[b, t]] + pe[t]), the target embedding of position t, on the LayerNorm
+//                       forward's row function (csa_ln_row.hpp): bitwise the gather + add + csa_layernorm_fwd
+// A counter outside its range makes the launch store nothing and read no row.
+//
 // M = 1, so there is no matrix product to feed an MFMA: both kernels are bound by memory latency (a few
 // hundred KB to a few tens of MB per launch) and are written for wave64 with 16-byte global loads.
 //
@@ -23,6 +31,7 @@
 // Append mode: the wave copies k_new / v_new into cache row t and reads key t from k_new / v_new themselves,
 // never from the row it has just stored (no read-after-write through global memory).
 #include "csa_common.hpp"
+#include "csa_ln_row.hpp"
 #include "../../include/csa_hip.h"
 
 #include <math.h>
@@ -38,6 +47,7 @@ constexpr int ARG_T = 256;
 
 struct DecArgs {
   int BH, H, hd, len, t;  // t < 0: no append
+  const int32_t* t_dev;   // device-stepped append: t = *t_dev, len (the capacity here) becomes t + 1
   const float* q; int64_t q_sb, q_sh;
   float* K; int64_t k_sb, k_sh, k_sn;
   float* V; int64_t v_sb, v_sh, v_sn;
@@ -64,6 +74,12 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
   __shared__ float ps[DEC_WAVES][64];
   __shared__ f32x4 red[DEC_WAVES][64];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int t = a.t, len = a.len;
+  if (a.t_dev) {  // one value for the whole grid: every wave of every workgroup leaves here, before any barrier
+    t = *a.t_dev;
+    if (t < 0 || t >= a.len) return;
+    len = t + 1;
+  }
   const int bh_raw = blockIdx.x * DEC_WAVES + w;
   // the workgroup's barriers need every wave: a wave past the last (b, h) redoes the last pair and stores nothing
   const bool valid = bh_raw < a.BH;
@@ -71,7 +87,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
   const int b = bh / a.H, h = bh - b * a.H;
   const int DC = a.hd >> 2;   // float4 column groups per row (<= 32)
   const int KG = 64 / DC;     // key groups of the P.V phase (>= 2)
-  const bool append = a.t >= 0;
+  const bool append = t >= 0;
 
   const float* qrow = a.q + b * a.q_sb + h * a.q_sh;
   float* Kb = a.K + b * a.k_sb + h * a.k_sh;
@@ -83,8 +99,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
   if (lane < DC) {
     qs[w][lane] = reinterpret_cast<const f32x4*>(qrow)[lane];
     if (append && valid) {  // this step's key / value row -> cache row t (rows above t are never touched)
-      reinterpret_cast<f32x4*>(Kb + (int64_t)a.t * a.k_sn)[lane] = reinterpret_cast<const f32x4*>(knew)[lane];
-      reinterpret_cast<f32x4*>(Vb + (int64_t)a.t * a.v_sn)[lane] = reinterpret_cast<const f32x4*>(vnew)[lane];
+      reinterpret_cast<f32x4*>(Kb + (int64_t)t * a.k_sn)[lane] = reinterpret_cast<const f32x4*>(knew)[lane];
+      reinterpret_cast<f32x4*>(Vb + (int64_t)t * a.v_sn)[lane] = reinterpret_cast<const f32x4*>(vnew)[lane];
     }
   }
   __syncthreads();
@@ -94,12 +110,12 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
   float m = -INFINITY, l = 0.f;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 
-  for (int j0 = 0; j0 < a.len; j0 += 64) {
+  for (int j0 = 0; j0 < len; j0 += 64) {
     // ---- scores of keys j0 .. j0 + 63 (lane = key) ----
     const int j = j0 + lane;
-    const bool in = j < a.len;
-    const int jc = in ? j : a.len - 1;  // always a readable row; the value is dropped below
-    const float* krow = (append && jc == a.t) ? knew : Kb + (int64_t)jc * a.k_sn;
+    const bool in = j < len;
+    const int jc = in ? j : len - 1;  // always a readable row; the value is dropped below
+    const float* krow = (append && jc == t) ? knew : Kb + (int64_t)jc * a.k_sn;
     float s = 0.f;
 #pragma unroll 8
     for (int c = 0; c < DC; ++c) {
@@ -129,7 +145,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] *= alpha;
       // ---- acc += P V over this chunk's keys (lane = key group x float4 column group) ----
-      const int nk = (a.len - j0 < 64) ? a.len - j0 : 64;
+      const int nk = (len - j0 < 64) ? len - j0 : 64;
       if (pv_lane) {
         // PV_U rows in flight per lane: the loads of a group are independent (issued together, row index clamped
         // to a real row and the value zeroed past the chunk), the FMAs keep the key order
@@ -142,7 +158,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
             const bool ok = ju < nk;
             const int jl = ok ? ju : jj;
             const int jk = j0 + jl;
-            const float* vrow = (append && jk == a.t) ? vnew : Vb + (int64_t)jk * a.v_sn;
+            const float* vrow = (append && jk == t) ? vnew : Vb + (int64_t)jk * a.v_sn;
             const f32x4 x = reinterpret_cast<const f32x4*>(vrow)[dc];
             pj[u] = ok ? ps[w][jl] : 0.f;
 #pragma unroll
@@ -178,18 +194,14 @@ __device__ __forceinline__ void arg_merge(float& v, int64_t& i, float vo, int64_
   if (vo > v || (vo == v && io < i)) { v = vo; i = io; }
 }
 
-__global__ __launch_bounds__(ARG_T) void k_argmax_rows(const float* __restrict__ x, int64_t V, int64_t* __restrict__ idx,
-                                                      int64_t idx_stride, uint8_t* __restrict__ is_pad,
-                                                      int64_t pad_stride, int64_t pad_id, float* __restrict__ maxval) {
+// The row's (maximum, lowest index of it), valid in thread 0 of the workgroup; ARG_T threads, all of them call.
+__device__ __forceinline__ void argmax_row(const float* __restrict__ xr, int64_t V, bool vec, float& v, int64_t& i) {
   __shared__ float rv[ARG_T / 64];
   __shared__ int64_t ri[ARG_T / 64];
-  const int64_t row = blockIdx.x;
-  const float* xr = x + row * V;
   // a thread walks its columns in increasing order with a strict >, so it keeps the lowest index of its maximum;
   // i = V marks "nothing above -inf seen" and loses every tie against a real index
-  float v = -INFINITY;
-  int64_t i = V;
-  const bool vec = (V % 4 == 0) && (((uintptr_t)x) & 15) == 0;
+  v = -INFINITY;
+  i = V;
   if (vec) {
     for (int64_t c = 4 * (int64_t)threadIdx.x; c < V; c += 4 * ARG_T) {
       const f32x4 q = *reinterpret_cast<const f32x4*>(xr + c);
@@ -215,10 +227,79 @@ __global__ __launch_bounds__(ARG_T) void k_argmax_rows(const float* __restrict__
 #pragma unroll
     for (int k = 1; k < ARG_T / 64; ++k) arg_merge(v, i, rv[k], ri[k]);
     if (i >= V) i = 0;  // all -inf (or NaN): index 0, always inside [0, V)
+  }
+}
+
+__global__ __launch_bounds__(ARG_T) void k_argmax_rows(const float* __restrict__ x, int64_t V, int64_t* __restrict__ idx,
+                                                      int64_t idx_stride, uint8_t* __restrict__ is_pad,
+                                                      int64_t pad_stride, int64_t pad_id, float* __restrict__ maxval) {
+  const int64_t row = blockIdx.x;
+  float v;
+  int64_t i;
+  argmax_row(x + row * V, V, (V % 4 == 0) && (((uintptr_t)x) & 15) == 0, v, i);
+  if (threadIdx.x == 0) {
     idx[row * idx_stride] = i;
     if (is_pad) is_pad[row * pad_stride] = (i == pad_id) ? 1 : 0;
     if (maxval) maxval[row] = v;
   }
+}
+
+// k_argmax_rows with the destination column t + 1 read from the device counter: ys[r, t+1], pad[r, t+1] and, for a
+// (rows, H, T) per-head mask viewed as (H, rows, T), head_pad[h, r, t+1] for every h (what BaseDecoder.step copies
+// from pad at the top of step t + 1). A column outside [1, T) stores nothing.
+__global__ __launch_bounds__(ARG_T) void k_argmax_rows_step(const float* __restrict__ x, int64_t V, int64_t* __restrict__ ys,
+                                                           int64_t ys_stride, int64_t T, uint8_t* __restrict__ pad,
+                                                           int64_t pad_stride, uint8_t* __restrict__ head_pad, int H,
+                                                           int64_t pad_id, const int32_t* __restrict__ t_dev) {
+  const int64_t col = (int64_t)*t_dev + 1;
+  if (col < 1 || col >= T) return;  // the whole grid, before the barrier
+  const int64_t row = blockIdx.x, rows = gridDim.x;
+  float v;
+  int64_t i;
+  argmax_row(x + row * V, V, (V % 4 == 0) && (((uintptr_t)x) & 15) == 0, v, i);
+  if (threadIdx.x == 0) {
+    const uint8_t p = (i == pad_id) ? 1 : 0;
+    ys[row * ys_stride + col] = i;
+    if (pad) pad[row * pad_stride + col] = p;
+    if (head_pad)
+      for (int h = 0; h < H; ++h) head_pad[((int64_t)h * rows + row) * T + col] = p;
+  }
+}
+
+// x[b] = LayerNorm(W[ys[b, t]] + pe[t]) for the position t read from the device counter (Embeddings.step): one wave
+// per row, the gathered row in registers, normalised by the LayerNorm forward's own row function. pe may be null
+// (no positional term). A token id outside [0, vocab) is clamped; a t outside [0, t_end) stores nothing.
+template <int CPL>
+__global__ __launch_bounds__(256) void k_decode_embed(const int64_t* __restrict__ ys, int64_t ys_stride, int64_t B,
+                                                      int64_t t_end, const int32_t* __restrict__ t_dev,
+                                                      const float* __restrict__ W, int64_t vocab,
+                                                      const float* __restrict__ pe, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float eps, float* __restrict__ x,
+                                                      int E) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t t = *t_dev;
+  if (t < 0 || t >= t_end || row >= B) return;
+  int64_t id = ys[row * ys_stride + t];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const float* wr = W + id * E;
+  const float* pr = pe ? pe + t * E : nullptr;
+  f32x4 v[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int c = 4 * (lane + 64 * q);
+    v[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c < E) {
+      v[q] = *reinterpret_cast<const f32x4*>(wr + c);
+      if (pr) {
+        const f32x4 p = *reinterpret_cast<const f32x4*>(pr + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[q][e] += p[e];
+      }
+    }
+  }
+  float mean, rstd;
+  ln_row_fwd<CPL>(v, lane, E, eps, gamma, beta, x + row * E, mean, rstd);
 }
 
 csa_status dfail(csa_status s, const char* m) {
@@ -229,30 +310,35 @@ csa_status dfail(csa_status s, const char* m) {
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 inline bool m4(int64_t s) { return s % 4 == 0; }
 
-}  // namespace
-
-extern "C" {
-
-int csa_decode_attn_supported(int64_t hd) { return (hd >= 4 && hd <= DEC_MAX_HD && hd % 4 == 0) ? 1 : 0; }
-
-csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream) {
-  if (!a) return dfail(CSA_INVALID_ARG, "csa_decode_attn: null args");
+// csa_decode_attn (step == false: host t, len = key count) and csa_decode_attn_step (step == true: t read from
+// t_dev by the kernel, len = the capacity of K / V / mask): one validation, one kernel.
+csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool step, const int32_t* t_dev, void* stream) {
+  const auto fail = [fn](csa_status s, const char* m) {
+    csa::set_error("%s: %s", fn, m);
+    return s;
+  };
+  if (!a) return fail(CSA_INVALID_ARG, "null args");
   if (a->B < 0 || a->H < 1 || a->len < 1 || a->B * a->H > 0x7fffffff || a->len > 0x7fffffff)
-    return dfail(CSA_INVALID_ARG, "csa_decode_attn: B, H, len must be positive (len >= 1)");
-  if (!csa_decode_attn_supported(a->hd))
-    return dfail(CSA_UNSUPPORTED_SHAPE, "csa_decode_attn: hd must be a multiple of 4 in [4, 128]");
+    return fail(CSA_INVALID_ARG, "B, H, len must be positive (len >= 1)");
+  if (!csa_decode_attn_supported(a->hd)) return fail(CSA_UNSUPPORTED_SHAPE, "hd must be a multiple of 4 in [4, 128]");
   const bool append = a->k_new || a->v_new;
-  if (append && (!a->k_new || !a->v_new)) return dfail(CSA_INVALID_ARG, "csa_decode_attn: k_new and v_new go together");
-  if (append && (a->t < 0 || a->t + 1 != a->len))
-    return dfail(CSA_INVALID_ARG, "csa_decode_attn: append mode needs len == t + 1");
+  if (append && (!a->k_new || !a->v_new)) return fail(CSA_INVALID_ARG, "k_new and v_new go together");
+  if (step) {
+    if (!append) return fail(CSA_INVALID_ARG, "k_new and v_new are required");
+    if (!t_dev || (((uintptr_t)t_dev) & 3)) return fail(CSA_INVALID_ARG, "t_dev must be a 4-byte aligned device pointer");
+  } else if (append && (a->t < 0 || a->t + 1 != a->len)) {
+    return fail(CSA_INVALID_ARG, "append mode needs len == t + 1");
+  }
   if (a->B == 0) return CSA_OK;
-  if (!a->q || !a->K || !a->V || !a->out) return dfail(CSA_INVALID_ARG, "csa_decode_attn: null pointer");
+  if (!a->q || !a->K || !a->V || !a->out) return fail(CSA_INVALID_ARG, "null pointer");
   if (!al16(a->q) || !al16(a->K) || !al16(a->V) || !al16(a->out) || !al16(a->k_new) || !al16(a->v_new) ||
       !m4(a->q_sb) || !m4(a->q_sh) || !m4(a->k_sb) || !m4(a->k_sh) || !m4(a->k_sn) || !m4(a->v_sb) || !m4(a->v_sh) ||
       !m4(a->v_sn) || (append && (!m4(a->kn_sb) || !m4(a->kn_sh) || !m4(a->vn_sb) || !m4(a->vn_sh))))
-    return dfail(CSA_INVALID_ARG, "csa_decode_attn: pointers must be 16-byte aligned and strides multiples of 4 elements");
+    return fail(CSA_INVALID_ARG, "pointers must be 16-byte aligned and strides multiples of 4 elements");
   DecArgs d;
-  d.BH = (int)(a->B * a->H); d.H = (int)a->H; d.hd = (int)a->hd; d.len = (int)a->len; d.t = append ? (int)a->t : -1;
+  d.BH = (int)(a->B * a->H); d.H = (int)a->H; d.hd = (int)a->hd; d.len = (int)a->len;
+  d.t = step ? 0 : (append ? (int)a->t : -1);
+  d.t_dev = step ? t_dev : nullptr;
   d.q = a->q; d.q_sb = a->q_sb; d.q_sh = a->q_sh;
   d.K = a->K; d.k_sb = a->k_sb; d.k_sh = a->k_sh; d.k_sn = a->k_sn;
   d.V = a->V; d.v_sb = a->v_sb; d.v_sh = a->v_sh; d.v_sn = a->v_sn;
@@ -266,7 +352,54 @@ csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream) {
   hipLaunchKernelGGL(k_decode_attn, dim3((unsigned)((d.BH + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, st, d);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    csa::set_error("csa_decode_attn: %s", hipGetErrorString(e));
+    csa::set_error("%s: %s", fn, hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csa_decode_attn_supported(int64_t hd) { return (hd >= 4 && hd <= DEC_MAX_HD && hd % 4 == 0) ? 1 : 0; }
+
+csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream) {
+  return decode_attn_impl("csa_decode_attn", a, false, nullptr, stream);
+}
+
+csa_status csa_decode_attn_step(const csa_decode_attn_args* a, const int32_t* t_dev, void* stream) {
+  return decode_attn_impl("csa_decode_attn_step", a, true, t_dev, stream);
+}
+
+csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int64_t T, const int32_t* t_dev,
+                            const float* W, int64_t vocab, const float* pe, int64_t max_len, const float* gamma,
+                            const float* beta, float eps, float* x, int64_t E, void* stream) {
+  const int cpl = ln_cpl(E);
+  if (cpl == 0) return dfail(CSA_UNSUPPORTED_SHAPE, "csa_decode_embed: E must be a multiple of 4 in [4, 1024]");
+  if (B < 0 || B > 0x7fffffff || T < 1 || vocab < 1 || (pe && max_len < 1) || ys_stride < T)
+    return dfail(CSA_INVALID_ARG, "csa_decode_embed: bad B / T / vocab / max_len / ys_stride");
+  if (!ys || !t_dev || !W || !gamma || !beta || !x) return dfail(CSA_INVALID_ARG, "csa_decode_embed: null pointer");
+  if ((((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3) || !al16(W) || !al16(pe) || !al16(gamma) || !al16(beta) || !al16(x))
+    return dfail(CSA_INVALID_ARG, "csa_decode_embed: misaligned pointer (ys 8, t_dev 4, the fp32 rows 16 bytes)");
+  if (B == 0) return CSA_OK;
+  const int64_t t_end = (pe && max_len < T) ? max_len : T;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  const dim3 grid((unsigned)((B + 3) / 4));
+#define CSA_EMBED_LAUNCH(C)                                                                                         \
+  hipLaunchKernelGGL(k_decode_embed<C>, grid, dim3(256), 0, st, ys, ys_stride, B, t_end, t_dev, W, vocab, pe, gamma, \
+                     beta, eps, x, (int)E)
+  switch (cpl) {
+    case 1: CSA_EMBED_LAUNCH(1); break;
+    case 2: CSA_EMBED_LAUNCH(2); break;
+    case 3: CSA_EMBED_LAUNCH(3); break;
+    default: CSA_EMBED_LAUNCH(4);
+  }
+#undef CSA_EMBED_LAUNCH
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_decode_embed: %s", hipGetErrorString(e));
     return CSA_LAUNCH_FAILED;
   }
   return CSA_OK;
@@ -285,6 +418,28 @@ csa_status csa_argmax_rows(const float* x, int64_t rows, int64_t V, int64_t* idx
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     csa::set_error("csa_argmax_rows: %s", hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
+                                uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
+                                const int32_t* t_dev, void* stream) {
+  if (rows < 0 || V < 1 || rows > 0x7fffffff || T < 1 || ys_stride < T || (pad && pad_stride < T) ||
+      (head_pad && (H < 1 || H > 0x7fffffff)))
+    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: bad rows / V / T / strides / H");
+  if (!x || !ys || !t_dev) return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: null pointer");
+  if ((((uintptr_t)x) & 3) || (((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3))
+    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: misaligned pointer");
+  if (rows == 0) return CSA_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad, pad_stride,
+                     head_pad, (int)H, pad_id, t_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_argmax_rows_step: %s", hipGetErrorString(e));
     return CSA_LAUNCH_FAILED;
   }
   return CSA_OK;

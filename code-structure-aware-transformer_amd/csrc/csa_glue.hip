@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "csa_common.hpp"
+#include "csa_ln_row.hpp"
 #include "../../include/csa_hip.h"
 
 using csa::f32x4;
@@ -99,7 +100,8 @@ inline int bg_slices(int64_t rows) {
 // ------------------------------------------------------------------------------------
 // LayerNorm over the last dim (nn.LayerNorm(size), eps 1e-5, the encoder's pre-norm sublayers):
 // one wave per row, the row in registers (CPL dwordx4 chunks per lane, cols <= 256 CPL), two-pass
-// mean / variance in registers (no E[x^2] - mean^2 cancellation). Backward: dx per row from the
+// mean / variance in registers (no E[x^2] - mean^2 cancellation): csa::ln_row_fwd (csa_ln_row.hpp, shared
+// with the decode step's embedding kernel). Backward: dx per row from the
 // saved (mean, rstd); dgamma / dbeta as per-workgroup column partials (fixed order) summed by
 // k_bias_grad_sum, so the whole backward is deterministic.
 // ------------------------------------------------------------------------------------
@@ -120,38 +122,13 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ x, con
   if (row >= rows) return;
   const float* xr = x + row * cols;
   f32x4 v[CPL];
-  float s = 0.f;
 #pragma unroll
   for (int q = 0; q < CPL; ++q) {
     const int c = 4 * (lane + 64 * q);
     v[q] = c < cols ? *reinterpret_cast<const f32x4*>(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    s += (v[q][0] + v[q][1]) + (v[q][2] + v[q][3]);
   }
-  const float mean = wave_sum(s) / (float)cols;
-  float ss = 0.f;
-#pragma unroll
-  for (int q = 0; q < CPL; ++q) {
-    const int c = 4 * (lane + 64 * q);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d = c < cols ? v[q][e] - mean : 0.f;
-      ss = fmaf(d, d, ss);
-    }
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)cols + eps);
-  float* yr = y + row * cols;
-#pragma unroll
-  for (int q = 0; q < CPL; ++q) {
-    const int c = 4 * (lane + 64 * q);
-    if (c < cols) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(beta + c);
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = fmaf((v[q][e] - mean) * rstd, g[e], b[e]);
-      *reinterpret_cast<f32x4*>(yr + c) = o;
-    }
-  }
+  float mean, rstd;
+  csa::ln_row_fwd<CPL>(v, lane, cols, eps, gamma, beta, y + row * cols, mean, rstd);
   if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
@@ -222,11 +199,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ dy, co
   }
 }
 
-inline int ln_cpl(int64_t cols) {
-  if (cols < 4 || cols % 4) return 0;
-  const int64_t cpl = (cols + 255) / 256;
-  return cpl <= 4 ? (int)cpl : 0;
-}
+using csa::ln_cpl;
 
 }  // namespace
 

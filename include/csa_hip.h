@@ -17,6 +17,8 @@
  *   csa_layernorm_fwd/_bwd  nn.LayerNorm of the encoder glue (module/components.py SublayerConnection)
  *   csa_ast_relations  my_ast.py:198-273 + dataset/base_data_set.py:33-36 (host C++, no GPU)
  *   csa_decode_attn / csa_argmax_rows  module/base_seq2seq.py:117-145 GreedyGenerator, one KV-cached decode step
+ *                      (and their device-stepped forms for a captured step: csa_decode_attn_step, csa_decode_embed,
+ *                      csa_argmax_rows_step)
  *
  * Conventions (all entry points):
  *   - fp32 data; device pointers; sizes and strides are int64 ELEMENT counts; the last
@@ -299,6 +301,30 @@ csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream);
  * row maximum. The eval-mode Generator's log(softmax(z)) is monotone in z, so this is its torch.max(out, 1)[1]. */
 csa_status csa_argmax_rows(const float* x, int64_t rows, int64_t V, int64_t* idx, int64_t idx_stride, uint8_t* is_pad,
                            int64_t pad_stride, int64_t pad_id, float* maxval, void* stream);
+
+/* ---- v10 additions: device-stepped decoding (one captured HIP graph replayed for every step of a batch) ----
+ * The step index t is read ON THE DEVICE from t_dev (one int32 shared by all rows, 4-byte aligned), so a launch
+ * does not depend on the step. None of the three syncs or allocates; a value of t outside the stated range makes
+ * the launch store nothing and read no row.
+ *
+ * csa_decode_attn_step: append-mode csa_decode_attn with t = *t_dev and t + 1 keys. a->len is the CAPACITY (the rows
+ * K / V and the mask hold), a->t is ignored, k_new / v_new are required. For equal t, out and the stored cache row
+ * are bitwise those of csa_decode_attn. Valid t: [0, capacity). */
+csa_status csa_decode_attn_step(const csa_decode_attn_args* a, const int32_t* t_dev, void* stream);
+/* x[b, :] = LayerNorm(W[ys[b * ys_stride + t], :] + pe[t, :]) (gamma, beta, eps), the Embeddings row of target
+ * position t: ys (B, T) int64 token buffer with a row stride, W (vocab, E), pe (max_len, E) or NULL for no positional
+ * term, x (B, E) contiguous; E as csa_layernorm_supported. Bitwise the gather + add + csa_layernorm_fwd (the same row
+ * reduction). A token id outside [0, vocab) is clamped into it. Valid t: [0, min(T, max_len)). */
+csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int64_t T, const int32_t* t_dev,
+                            const float* W, int64_t vocab, const float* pe, int64_t max_len, const float* gamma,
+                            const float* beta, float eps, float* x, int64_t E, void* stream);
+/* csa_argmax_rows with the destination column chosen on the device: ys[r * ys_stride + t + 1] = the row argmax (same
+ * tie rule), pad[r * pad_stride + t + 1] = (index == pad_id) when pad is given, and when head_pad is given (a
+ * contiguous (rows, H, T) byte mask) the same byte at head_pad[(h * rows + r) * T + t + 1] for every h < H: the
+ * (H, rows, T) view in which the decoder key-pads its heads. Valid t + 1: [1, T). */
+csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
+                                uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
+                                const int32_t* t_dev, void* stream);
 
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
