@@ -269,9 +269,11 @@ struct FragJob {
   const float* src; float* dst;
   int rows, cols, ld;         // source matrix (rows x cols, row stride ld)
   int transpose;              // value = src[kk][r] instead of src[r][kk]
-  int acc_perm;               // kperm: 0 = lin (k = s + nsteps*h), 1 = acc (k = 32(s/16)+crow(s%16,h))
+  int acc_perm;               // kperm: 0 = lin (k = s + nsteps*h), 1 = acc (k = 32(s/16)+crow(s%16,h)),
+                              // 2 = the 16x16x4 MFMA's (k = 4 (lane >> 4) + s, one instruction per step)
   int nit, nsteps;            // output tiles x K-steps
   int batch; int64_t src_bstride, dst_bstride;  // repeated per head
+  int lanes16;                // 16-row operand of the 16-wide MFMAs: row = lane & 15 (else 32 it + (lane & 31))
 };
 struct FragJobs { FragJob j[12]; int n; };
 
@@ -282,9 +284,10 @@ __device__ __forceinline__ void frag_elem(const FragJob& J, int64_t e) {
   const int s4 = (int)(rem / 256) % (J.nsteps / 4);
   const int it = (int)(rem / 256) / (J.nsteps / 4);
   const int lane = (int)(rem / 4) % 64, s = s4 * 4 + (int)(rem % 4);
-  const int c = lane & 31, h = lane >> 5;
+  const int c = J.lanes16 ? lane & 15 : lane & 31, h = lane >> 5;
   const int r = 32 * it + c;
-  const int kk = J.acc_perm ? 32 * (s / 16) + crow(s % 16, h) : s + J.nsteps * h;
+  const int kk = J.acc_perm == 2 ? 4 * (lane >> 4) + s
+                                 : J.acc_perm ? 32 * (s / 16) + crow(s % 16, h) : s + J.nsteps * h;
   const float* src = J.src + bidx * J.src_bstride;
   float v = 0.f;
   if (r < J.rows && kk < J.cols) v = J.transpose ? src[(int64_t)kk * J.ld + r] : src[(int64_t)r * J.ld + kk];
@@ -540,6 +543,73 @@ __device__ __forceinline__ void small_mm(const float* __restrict__ frag, const f
   frag_chain<KT, 4 * KT, 1, FL>(frag, 16 * KT, out, [&](int s) { return in[s / 16][s % 16]; });
 }
 
+// kp = 16 (k <= 16), fp32: the cluster products at their true width. A 32x32 tile spends half of its rows on
+// clusters 16 .. 31, which do not exist: they are multiplied, run through the sigmoid and stored as zeros. The
+// 16-wide MFMAs (csa_common.hpp) put the cluster index on 16 lanes instead, at half the pipe cycles.
+// "Hat layout": lane l holds clusters 4 (l >> 4) .. + 3 of data rows l & 15 (half 0) and 16 + (l & 15) (half 1).
+//
+// hat^T = sigmoid(C_h p^T) on mfma4b, one instruction per K-step s of the acc permutation. Lane l feeds
+// B = its own po[s / 16][s % 16] and A = C[l & 15][32 (s / 16) + crow(s % 16, l >> 5)] (k_prep's lanes16 fragment,
+// one b128 per lane per 4 steps), so block l >> 4 covers data rows 16 ((l >> 4) & 1) + (l & 15) and the feature half
+// l >> 5: blocks b and b + 2 hold the two feature halves' partial sums of row half b (as store_mb4's).
+// Even and odd K-steps go to two accumulator sets E and O: an instruction then depends on the one two before it
+// (64 cycles of issue against the 16-wide MFMAs' 40-cycle dependent latency) instead of stalling on its
+// predecessor. Summation order: each of E_b, O_b, E_b+2, O_b+2 is a chain over its K-steps in ascending order, and
+// hat = (E_b + O_b) + (E_b+2 + O_b+2).
+template <int D, bool FL>
+__device__ __forceinline__ void cluster_hat16(const KArgs& p, const float* Cf, const f32x16 (&po)[D / 32], f32x4 (&hat)[2]) {
+  constexpr int NS = D / 2, S4N = NS / 4;
+  auto ld = [&](int s4) { return FL ? frag4_lds(Cf, 0, NS, s4) : frag4(Cf, 0, NS, s4); };
+  f32x16 acc[2] = {zero16(), zero16()};
+  f32x4 wq[2];
+  wq[0] = ld(0);
+#pragma unroll
+  for (int s4 = 0; s4 < S4N; ++s4) {
+    if (s4 + 1 < S4N) wq[(s4 + 1) & 1] = ld(s4 + 1);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int s = 4 * s4 + e;
+      acc[e & 1] = mfma4b(wq[s4 & 1][e], po[s / 16][s % 16], acc[e & 1]);
+    }
+    if constexpr (FL) {  // as frag_chain: the lookahead read ahead of the group's MFMAs
+      if (s4 + 1 < S4N) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+    }
+    fence_sched();
+  }
+  const int cl = 4 * (lane_id() >> 4);
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float z = (acc[0][4 * b + e] + acc[1][4 * b + e]) + (acc[0][8 + 4 * b + e] + acc[1][8 + 4 * b + e]);
+      // sigmoid via hardware exp / divide (a few ulp; branch-free): sbm_attn.py:47,53
+      hat[b][e] = (cl + e < p.k) ? __fdividef(1.f, 1.f + __expf(-z)) : 0.f;
+    }
+}
+
+// T^T = S hat^T on mfma16: the hat layout is that instruction's B operand (K index 4 (l >> 4) + e at step e), the
+// A operand is k_prep's 1 KiB fragment S[l & 15][4 (l >> 4) + e], and the result has the hat layout again. The two
+// row halves alternate, so no instruction waits on its predecessor.
+template <bool FL>
+__device__ __forceinline__ void small_mm16(const float* __restrict__ Sf, const f32x4 (&hat)[2], f32x4 (&t)[2]) {
+  const f32x4 sa = FL ? frag4_lds(Sf, 0, 4, 0) : frag4(Sf, 0, 4, 0);
+  t[0] = t[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) t[b] = mfma16(sa[e], hat[b][e], t[b]);
+}
+
+// Hat-layout values of a 32-row block -> out[row][0..16) (out: the block's first row; rows >= nrows are skipped):
+// one 16-byte store per lane and row half, 1 KiB contiguous per half.
+__device__ __forceinline__ void store_rows16(float* __restrict__ out, int nrows, const f32x4 (&a)[2]) {
+  const int l = lane_id(), rr = l & 15, cl = 4 * (l >> 4);
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+    if (16 * b + rr < nrows) *reinterpret_cast<f32x4*>(out + (16 * b + rr) * 16 + cl) = a[b];
+}
+
 // Store an accumulator tile set (feature rows, data row = lane) to out[row][0..ncols) (row-major, ld)
 template <int NT>
 __device__ __forceinline__ void store_rows(float* __restrict__ out, int64_t ld, int ncols, const f32x16 (&a)[NT], bool valid) {
@@ -752,7 +822,9 @@ __device__ __forceinline__ void load_item_x(const KArgs& p, int b, int hd, int r
 // F2 body: item r of (b, hd) from its x rows. `next` runs once every product is done and x is dead,
 // before the stores (the persistent kernel issues the next item's x loads there: a later vmcnt wait
 // for them then does not also wait for this item's stores, which drain under the next item).
-template <int D, int KT, bool FL, typename NEXT, bool BF = false, bool PD = true>
+// W16 (fp32, KT = 1, kp = 16): the cluster products on the 16-wide MFMAs (cluster_hat16); F.C / F.S are then the
+// lanes16 fragments.
+template <int D, int KT, bool FL, typename NEXT, bool BF = false, bool PD = true, bool W16 = false>
 __device__ __forceinline__ void proj_fwd_item(const KArgs& p, const FwdFrags& F, int b, int hd, int r, float (&x)[D / 2],
                                               float* scr, NEXT next) {
   const int lane = lane_id(), c = lane & 31, h = lane >> 5;
@@ -804,6 +876,21 @@ __device__ __forceinline__ void proj_fwd_item(const KArgs& p, const FwdFrags& F,
   PHF(2)
   mlp_layer<D, FL, BF>(F.W[2], F.b[2], h2, po, Side{{ars, 32 * D * 4, scr, h2, {}}});
   PHF(3)
+  if constexpr (W16) {
+    // h2c_path: po is not saved, and k_proj_bwd_s reads hat from the Qh / Kh rows: nothing but those rows leaves here
+    static_assert(!BF && KT == 1 && h2c_path(D, KT, BF), "W16: the fp32 k <= 16 kernels");
+    f32x4 hat16[2], t16[2];
+    cluster_hat16<D, FL>(p, F.C, po, hat16);
+    if (isK) small_mm16<FL>(F.S, hat16, t16);
+    next();
+    if (!isK) {
+      store_rows16(p.Qh + ((int64_t)bh * p.N + rb * 32) * 16, nrows - rb * 32, hat16);
+    } else {
+      store_rows16(p.Kh + ((int64_t)bh * p.M + rb * 32) * 16, nrows - rb * 32, hat16);
+      store_rows16(p.T + ((int64_t)bh * p.M + rb * 32) * 16, nrows - rb * 32, t16);
+    }
+    return;
+  }
   // po is not saved when k_proj_bwd_s forms dC from h2 (h2c_path): its stager is skipped (wave-uniform branch)
   struct SideIf {
     ActStager<D / 32> st;
@@ -878,14 +965,16 @@ struct ProjFwdLds {
 };
 
 // BF: CSA_DTYPE_BF16 (MLP and cluster projection on bf16 MFMA; T = Kh S^T stays fp32)
-template <int D, int KT, bool BF = false, bool PD = true>
+// W16: kp = 16 in fp32 (proj_fwd_item): p.Cf / p.Sf hold the lanes16 fragments, S_hd's is 1 KiB of its 4 KiB slot
+template <int D, int KT, bool BF = false, bool PD = true, bool W16 = false>
 __global__ __launch_bounds__((64 * ProjFwdLds<D, KT>::NW)) void k_proj_fwd_l(const KArgs p) {
   using LY = ProjFwdLds<D, KT>;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int hd = blockIdx.y, g = blockIdx.x, G = gridDim.x;
   const uint32_t L0 = lds_offset(lds);
-  for (int pc = w; pc < LY::PIECES; pc += LY::NW) {  // 1 KiB pieces: W0 | W1 | W2 | C_hd | S_hd
+  constexpr int NPC = W16 ? LY::PIECES - LY::SB / 1024 + 1 : LY::PIECES;
+  for (int pc = w; pc < NPC; pc += LY::NW) {  // 1 KiB pieces: W0 | W1 | W2 | C_hd | S_hd
     const int byte = pc * 1024;
     const float* src;
     int off;
@@ -910,7 +999,7 @@ __global__ __launch_bounds__((64 * ProjFwdLds<D, KT>::NW)) void k_proj_fwd_l(con
     auto nextf = [&] {
       if (nx < i_hi) load_item_x<D>(p, nx / per_b, hd, nx % per_b, x);
     };
-    proj_fwd_item<D, KT, true, decltype(nextf), BF, PD>(p, F, it / per_b, hd, it % per_b, x, scr, nextf);
+    proj_fwd_item<D, KT, true, decltype(nextf), BF, PD, W16>(p, F, it / per_b, hd, it % per_b, x, scr, nextf);
   }
 }
 
@@ -3666,14 +3755,19 @@ csa_status launch_fwd(const csa_sbm_fwd_args* a, const Layout& L, hipStream_t st
   const int BH = (int)(a->B * a->H);
   if constexpr (KPH > 0) {
     const int KP32 = 32 * KT;
+    const bool w16 = !p.bf16 && KT == 1 && L.kp == 16;
     float* S = (float*)((char*)a->state + L.S);
     {
     Stage sg(a->prof, CSA_STAGE_PREP, st);
     FragJobs J;
     memset(&J, 0, sizeof(J));
     int n = 0;
-    J.j[n++] = FragJob{S, (float*)p.Sf, KP32, KP32, KP32, 0, 1, KT, 16 * KT, (int)a->H, (int64_t)KP32 * KP32,
-                       (int64_t)KP32 * KP32};
+    // w16: k_proj_fwd_l's cluster products run on the 16-wide MFMAs (proj_fwd_item W16), whose A operands replace
+    // the 32-row fragments in the same Sf / Cf slots (S's is 1 KiB of its 4 KiB); bf16 mode keeps the 32-row ones
+    J.j[n++] = w16 ? FragJob{S, (float*)p.Sf, KP32, KP32, KP32, 0, 2, 1, 4, (int)a->H, (int64_t)KP32 * KP32,
+                             (int64_t)KP32 * KP32, 1}
+                   : FragJob{S, (float*)p.Sf, KP32, KP32, KP32, 0, 1, KT, 16 * KT, (int)a->H, (int64_t)KP32 * KP32,
+                             (int64_t)KP32 * KP32};
     J.j[n++] = FragJob{S, (float*)p.SfT, KP32, KP32, KP32, 1, 1, KT, 16 * KT, (int)a->H, (int64_t)KP32 * KP32,
                        (int64_t)KP32 * KP32};
     const int nS = n;  // S_h's fragments: laid out by the head's softmax block
@@ -3684,7 +3778,7 @@ csa_status launch_fwd(const csa_sbm_fwd_args* a, const Layout& L, hipStream_t st
       J.j[n++] = FragJob{a->proj_w[l], (float*)p.WfT[l], D, D, D, 1, 1, D / 32, D / 2, 1, 0, 0};
     }
     J.j[n++] = FragJob{a->cluster_w, (float*)p.Cf, (int)a->k, D, D, 0, 1, KT, D / 2, (int)a->H, a->k * D,
-                       (int64_t)KP32 * D};
+                       (int64_t)KP32 * D, w16 ? 1 : 0};
     J.j[n++] = FragJob{a->cluster_w, (float*)p.CfT, D, (int)a->k, D, 1, 1, D / 32, 16 * KT, (int)a->H, a->k * D,
                        (int64_t)KP32 * D};
     J.n = n;
@@ -3702,18 +3796,21 @@ csa_status launch_fwd(const csa_sbm_fwd_args* a, const Layout& L, hipStream_t st
           const int64_t items = a->B * (L.NQB + L.NKB), slots = (D == 64 && PL::NW == 4 ? 2 : 1) * 256LL;
           const int G = (int)std::max<int64_t>(1, std::min<int64_t>(slots / a->H, (items + PL::NW - 1) / PL::NW));
           // (PD: the projection dropout's Philox words are drawn; without dropout they are not)
-#define CSA_PF_LAUNCH(BFV, PDV)                                                                         \
-  do {                                                                                                  \
-    set_dyn_lds((const void*)k_proj_fwd_l<D, KT, BFV, PDV>, (int)PL::BYTES);                            \
-    hipLaunchKernelGGL((k_proj_fwd_l<D, KT, BFV, PDV>), dim3(G, a->H), dim3(64 * PL::NW), PL::BYTES, st, p); \
+#define CSA_PF_LAUNCH(BFV, PDV, WV)                                                                         \
+  do {                                                                                                      \
+    set_dyn_lds((const void*)k_proj_fwd_l<D, KT, BFV, PDV, WV>, (int)PL::BYTES);                            \
+    hipLaunchKernelGGL((k_proj_fwd_l<D, KT, BFV, PDV, WV>), dim3(G, a->H), dim3(64 * PL::NW), PL::BYTES, st, p); \
   } while (0)
           const bool pd = a->proj_dropout > 0.f;
           if (p.bf16) {  // CSA_DTYPE_BF16: MLP + cluster projection on bf16 MFMA
-            if (pd) CSA_PF_LAUNCH(true, true);
-            else CSA_PF_LAUNCH(true, false);
+            if (pd) CSA_PF_LAUNCH(true, true, false);
+            else CSA_PF_LAUNCH(true, false, false);
+          } else if (w16) {
+            if (pd) CSA_PF_LAUNCH(false, true, true);
+            else CSA_PF_LAUNCH(false, false, true);
           } else {
-            if (pd) CSA_PF_LAUNCH(false, true);
-            else CSA_PF_LAUNCH(false, false);
+            if (pd) CSA_PF_LAUNCH(false, true, false);
+            else CSA_PF_LAUNCH(false, false, false);
           }
 #undef CSA_PF_LAUNCH
           done = true;
