@@ -142,6 +142,20 @@ class DecodeAttnArgs(ctypes.Structure):  # ABI v10
     ]
 
 
+class BeamSelectArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("B", i64), ("W", i64), ("T", i64),
+        ("topv", vp), ("topi", vp), ("lse", vp),
+        ("cum", vp), ("fin", vp),
+        ("tokens", vp), ("tok_stride", i64),
+        ("pad", vp), ("pad_stride", i64),
+        ("anc", vp), ("anc_stride", i64),
+        ("parent", vp),
+        ("eos_id", i64), ("pad_id", i64),
+        ("t_dev", vp),
+    ]
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -233,6 +247,14 @@ def lib():
     L.csa_decode_embed.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, f32, vp, i64, vp]
     L.csa_argmax_rows_step.restype = ctypes.c_int
     L.csa_argmax_rows_step.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, i64, vp, vp]
+    L.csa_beam_supported.restype = ctypes.c_int  # v10 additions: beam search over the device-stepped step
+    L.csa_beam_supported.argtypes = [i64, i64]
+    L.csa_beam_row_topk.restype = ctypes.c_int
+    L.csa_beam_row_topk.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, i64, vp]
+    L.csa_beam_select.restype = ctypes.c_int
+    L.csa_beam_select.argtypes = [ctypes.POINTER(BeamSelectArgs), vp]
+    L.csa_decode_attn_beam.restype = ctypes.c_int
+    L.csa_decode_attn_beam.argtypes = [ctypes.POINTER(DecodeAttnArgs), vp, vp, i64, i64, vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -262,4 +284,5 @@ EXPORTED_SYMBOLS = (
     "csa_collate_relations",
     "csa_decode_attn_supported", "csa_decode_attn", "csa_argmax_rows",
     "csa_decode_attn_step", "csa_decode_embed", "csa_argmax_rows_step",
+    "csa_beam_supported", "csa_beam_row_topk", "csa_beam_select", "csa_decode_attn_beam",
 )

@@ -7,13 +7,18 @@ Device-stepped calls (the captured decode step of CachedGreedyGenerator(graph=Tr
 csa_argmax_rows_step, csa_decode_embed) and the host never learns its value, so the same launch serves every step.
 
 fp32 CUDA tensors with a supported head dim run the HIP kernels; CPU tensors, other dtypes or an unsupported
-head dim run the same cached algorithm on F.scaled_dot_product_attention / torch.max over the same views."""
+head dim run the same cached algorithm on F.scaled_dot_product_attention / torch.max over the same views.
+
+Beam search (csrc/csa_beam.hip and the BEAM form of the attention kernel): decode_attention takes an ancestry table
+(anc=) or a row group sharing one memory (kv_group=), beam_row_topk gives each row's log-sum-exp and top-W logits and
+beam_select merges them per AST and rewrites the hypotheses' state in place. Each has the same kind of torch fallback,
+so the whole search also runs on the CPU."""
 import ctypes
 
 import torch
 import torch.nn.functional as F
 
-from ._lib import DecodeAttnArgs, check, lib, on_device
+from ._lib import BeamSelectArgs, DecodeAttnArgs, check, lib, on_device
 from .ops import _stream
 
 
@@ -34,7 +39,7 @@ def _check_step(t, device, what):
         raise ValueError(f"{what}: the device step must be a 1-element int32 tensor on the tensors' device")
 
 
-def _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None):
+def _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None, anc=None, kv_group=1):
     B, H, hd = q.shape
     if out is None:
         out = torch.empty(B, H * hd, device=q.device, dtype=torch.float32)
@@ -50,14 +55,18 @@ def _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, out
         a.k_new, a.kn_sb, a.kn_sh = _ptr(k_new), k_new.stride(0), k_new.stride(1)
         a.v_new, a.vn_sb, a.vn_sh = _ptr(v_new), v_new.stride(0), v_new.stride(1)
     with on_device(q.device):
-        if step:  # length is the capacity; the kernel reads t and attends to t + 1 keys
+        if anc is not None or kv_group != 1:
+            check(lib().csa_decode_attn_beam(ctypes.byref(a), _ptr(t) if step else None, _ptr(anc),
+                                             anc.stride(0) if anc is not None else 0, kv_group, _stream(q.device)),
+                  "csa_decode_attn_beam")
+        elif step:  # length is the capacity; the kernel reads t and attends to t + 1 keys
             check(lib().csa_decode_attn_step(ctypes.byref(a), _ptr(t), _stream(q.device)), "csa_decode_attn_step")
         else:
             check(lib().csa_decode_attn(ctypes.byref(a), _stream(q.device)), "csa_decode_attn")
     return out
 
 
-def _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None):
+def _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None, anc=None, kv_group=1):
     B, H, hd = q.shape
     if _is_step(t):  # the host reads the counter: not for a captured graph
         t, cap = int(t.item()), length
@@ -67,6 +76,15 @@ def _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, out
     if k_new is not None:
         K[:, :, t] = k_new
         V[:, :, t] = v_new
+    if anc is not None:  # key j < t of row r from cache row anc[r, j], key t from row r itself: a physical gather
+        rows = anc[:, :length].long().clone()
+        rows[:, t] = torch.arange(B, device=q.device)
+        ix = (rows[:, None, :], torch.arange(H, device=q.device)[None, :, None],
+              torch.arange(length, device=q.device)[None, None, :])
+        K, V = K[ix], V[ix]
+    elif kv_group != 1:  # the rows of a group share batch index r // kv_group
+        K, V = K.repeat_interleave(kv_group, 0), V.repeat_interleave(kv_group, 0)
+        key_mask = None if key_mask is None else key_mask.repeat_interleave(kv_group, 0)
     m = None
     if key_mask is not None:
         km = key_mask[..., :length].ne(0).view(B, -1, 1, length)  # (B, 1 | H, 1, length)
@@ -76,7 +94,8 @@ def _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, out
     return o if out is None else out.copy_(o)
 
 
-def decode_attention(q, K, V, length=None, key_mask=None, k_new=None, v_new=None, t=None, scale=None, out=None):
+def decode_attention(q, K, V, length=None, key_mask=None, k_new=None, v_new=None, t=None, scale=None, out=None,
+                     anc=None, kv_group=1):
     """Single-query attention of one decode step.
 
     q (B,H,hd); K, V (B,H,>=length,hd) views (any batch / head / key strides, hd contiguous); key_mask optional
@@ -88,8 +107,20 @@ def decode_attention(q, K, V, length=None, key_mask=None, k_new=None, v_new=None
     attends to t + 1 keys; length is then the CAPACITY (default K.shape[2]: the rows K, V and key_mask hold), and a
     step outside [0, capacity) stores nothing, neither the cache row nor the output. Off the HIP path the step is read
     on the host (t.item()) and the int path runs.
-    out: optional (B, H*hd) fp32 contiguous tensor to receive the result."""
+    out: optional (B, H*hd) fp32 contiguous tensor to receive the result.
+    Beam search, B = R hypothesis rows:
+    anc (R, >= length) int32, append mode only: key / value j < t of row r is read from cache row anc[r, j] instead of
+    row r (key t from k_new / v_new, stored at row r as always), the mask byte stays key_mask[r, j]; no cache row moves.
+    kv_group = W > 1, without anc: K, V and key_mask hold R / W batch rows and row r reads row r // W, the one memory
+    projection of its AST."""
     B, H, hd = q.shape
+    kv_group = int(kv_group)
+    if kv_group < 1 or (kv_group != 1 and (K.shape[0] * kv_group != B or V.shape[0] * kv_group != B)):
+        raise ValueError("decode_attention: kv_group must divide the rows of q, with K and V holding B / kv_group rows")
+    if anc is not None and (kv_group != 1 or k_new is None or anc.dtype != torch.int32 or anc.dim() != 2
+                            or anc.shape[0] != B or anc.stride(1) != 1 or anc.device != q.device):
+        raise ValueError("decode_attention: anc is a (B, >= length) int32 table on q's device with a contiguous last "
+                         "dim, for append mode with kv_group == 1")
     if (k_new is None) != (v_new is None) or (k_new is not None and t is None):
         raise ValueError("decode_attention: k_new, v_new and t go together")
     if _is_step(t):
@@ -105,11 +136,13 @@ def decode_attention(q, K, V, length=None, key_mask=None, k_new=None, v_new=None
         length = t + 1
     elif length is None:
         length = K.shape[2]
-    if not 1 <= length <= K.shape[2] or (key_mask is not None and key_mask.shape[-1] < length):
-        raise ValueError("decode_attention: length outside the keys / mask given")
+    if not 1 <= length <= K.shape[2] or (key_mask is not None and key_mask.shape[-1] < length) or (
+            anc is not None and anc.shape[1] < length):
+        raise ValueError("decode_attention: length outside the keys / mask / ancestry table given")
     if key_mask is not None and (key_mask.dtype != torch.uint8 or key_mask.stride(-1) != 1
-                                 or key_mask.shape[:-1] not in ((B,), (B, H))):
-        raise ValueError("decode_attention: key_mask must be (B, L) or (B, H, L) uint8 with a contiguous last dim")
+                                 or key_mask.shape[:-1] not in ((B // kv_group,), (B // kv_group, H))):
+        raise ValueError("decode_attention: key_mask must be (B, L) or (B, H, L) uint8 with a contiguous last dim "
+                         "(B / kv_group rows with a group)")
     scale = float(hd) ** -0.5 if scale is None else float(scale)
     ts = [x for x in (q, K, V, k_new, v_new) if x is not None]
     if any(x.stride(-1) != 1 for x in ts):
@@ -118,6 +151,8 @@ def decode_attention(q, K, V, length=None, key_mask=None, k_new=None, v_new=None
                             or not out.is_contiguous()):
         raise ValueError("decode_attention: out must be (B, H*hd) contiguous, of q's dtype and device")
     extra = () if out is None else (out,)
+    if anc is not None or kv_group != 1:
+        extra = (out, anc, kv_group)
     if _hip_ok(q, hd) and all(x.is_cuda and x.dtype == torch.float32 for x in ts):
         return _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, *extra)
     return _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, *extra)
@@ -230,3 +265,131 @@ def decode_embed(ys, t, emb):
     if not 0 <= tt < T:
         raise ValueError(f"decode_embed: step {tt} outside [0, {T})")
     return emb.step(ys[:, tt:tt + 1], tt)[:, 0]
+
+
+# ---- beam search: per-row top-W and log-sum-exp, per-AST merge with the in-place state update ----
+
+def _step_value(t, lo, hi, what):
+    """The host-side value of a step given as an int or a counter tensor (fallback paths only)."""
+    tt = int(t.item()) if _is_step(t) else int(t)
+    if not lo <= tt < hi:
+        raise ValueError(f"{what}: step {tt} outside [{lo}, {hi})")
+    return tt
+
+
+def _beam_row_topk_ref(z, W, lse, topv, topi):
+    zf = z.float()
+    lse.copy_(torch.logsumexp(zf, dim=1))
+    v, i = torch.sort(zf, dim=1, descending=True, stable=True)  # equal values keep their index order
+    topv.copy_(v[:, :W])
+    topi.copy_(i[:, :W])
+
+
+def beam_row_topk(z, W, lse=None, topv=None, topi=None, t_dev=None, t_end=None):
+    """Per row of the logits z (rows, V), V >= W: lse (rows,) fp32 = log sum exp, topv (rows, W) fp32 the W largest
+    logits in descending order and topi (rows, W) int32 their indices, the lowest index first among equal values (an
+    all -inf row gives 0 .. W-1). Returns (lse, topv, topi); the three are allocated unless given (contiguous).
+    t_dev (1-element int32 counter) with t_end: the HIP kernel stores nothing unless 0 <= t < t_end; off the HIP path
+    the host reads the counter and a step outside that range raises."""
+    rows, V = z.shape
+    W = int(W)
+    if not 1 <= W <= 8:
+        raise ValueError("beam_row_topk: the beam width must be in [1, 8]")
+    if V < W:
+        raise ValueError("beam_row_topk: V must be at least W")
+    if (t_dev is None) != (t_end is None):
+        raise ValueError("beam_row_topk: t_dev and t_end go together")
+    if t_dev is not None:
+        _check_step(t_dev, z.device, "beam_row_topk")
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=z.device)
+    lse = new((rows,), torch.float32) if lse is None else lse
+    topv = new((rows, W), torch.float32) if topv is None else topv
+    topi = new((rows, W), torch.int32) if topi is None else topi
+    for x, shape, dt in ((lse, (rows,), torch.float32), (topv, (rows, W), torch.float32), (topi, (rows, W), torch.int32)):
+        if x.shape != shape or x.dtype != dt or x.device != z.device or not x.is_contiguous():
+            raise ValueError("beam_row_topk: lse (rows,) fp32, topv (rows, W) fp32, topi (rows, W) int32, contiguous, "
+                             "on z's device")
+    if z.is_cuda and z.dtype == torch.float32 and z.is_contiguous():
+        with on_device(z.device):
+            check(lib().csa_beam_row_topk(_ptr(z), rows, V, W, _ptr(lse), _ptr(topv), _ptr(topi), _ptr(t_dev),
+                                          0 if t_end is None else int(t_end), _stream(z.device)), "csa_beam_row_topk")
+    else:
+        if t_dev is not None:
+            _step_value(t_dev, 0, int(t_end), "beam_row_topk")
+        _beam_row_topk_ref(z, W, lse, topv, topi)
+    return lse, topv, topi
+
+
+def _beam_select_ref(topv, topi, lse, cum, fin, tokens, pad, anc, t, eos_id, pad_id, parent):
+    R, W = topv.shape
+    B, dev = R // W, topv.device
+    live = fin.view(B, W, 1) == 0
+    score = cum.view(B, W, 1) + (topv.view(B, W, W) - lse.view(B, W, 1))
+    score = torch.where(live, score, cum.view(B, W, 1).expand(B, W, W))
+    score = torch.where(score > float("-inf"), score, torch.full_like(score, float("-inf")))  # NaN too
+    tok = torch.where(live, topi.view(B, W, W).long(), torch.full((B, W, W), pad_id, dtype=torch.long, device=dev))
+    offered = live | (torch.arange(W, device=dev).view(1, 1, W) == 0)
+    row = torch.arange(W, device=dev).view(1, W, 1).expand(B, W, W)
+    score, tok, offered, row = (x.reshape(B, W * W) for x in (score, tok, offered, row))
+    # score descending, then parent row, then token, the offered candidates first: stable sorts, last key first
+    order = torch.argsort(tok, dim=1, stable=True)
+    for key, desc in ((row, False), (score, True), (offered.to(torch.int8), True)):
+        order = order.gather(1, torch.argsort(key.gather(1, order), dim=1, descending=desc, stable=True))
+    best = order[:, :W]
+    p_local = row.gather(1, best)
+    prow = (p_local + W * torch.arange(B, device=dev).view(B, 1)).reshape(R)
+    new_tok = tok.gather(1, best).reshape(R)
+    new_fin = (fin[prow] != 0) | (new_tok == eos_id)
+    new_cum = score.gather(1, best).reshape(R)
+    tokens[:, :t + 1] = tokens[prow, :t + 1]
+    pad[:, :t + 1] = pad[prow, :t + 1]
+    anc[:, :t] = anc[prow, :t]
+    tokens[:, t + 1] = new_tok
+    pad[:, t + 1] = new_tok == pad_id
+    anc[:, t] = prow
+    cum.copy_(new_cum)
+    fin.copy_(new_fin)
+    if parent is not None:
+        parent.copy_(prow)
+
+
+def beam_select(topv, topi, lse, cum, fin, tokens, pad, anc, t, eos_id=None, pad_id=0, parent=None):
+    """One beam step of every AST, in place (rows r = b * W + w; W = topv.shape[1]).
+
+    topv / topi (R, W) and lse (R,) from beam_row_topk; cum (R,) fp32 and fin (R,) uint8 the hypotheses' cumulative
+    log-probability and finished flag; tokens (R, T) int64, pad (R, T) uint8 and anc (R, T) int32 (row strides free,
+    last dim contiguous) the token buffer, the PAD key mask and the ancestry table. A live row offers
+    (cum + (topv - lse), topi) W times, a finished row only (cum, pad_id); the best W per AST (score descending, then
+    parent row, then token) become its rows: a child takes its parent's columns 0..t of tokens and pad and 0..t-1 of
+    anc, then tokens[:, t+1], pad[:, t+1] = (token == pad_id), anc[:, t] = the parent row, cum and
+    fin = parent finished or token == eos_id (None: never). parent (R,) int32, optional, receives the parent rows.
+    t: the 1-element int32 counter (the HIP kernel reads it; a step outside [0, T-1) stores nothing) or an int."""
+    R, W = topv.shape
+    T = tokens.shape[1] if tokens.dim() == 2 else -1
+    dev = topv.device
+    eos = -1 if eos_id is None else int(eos_id)
+
+    def bad(x, shape, dt, contiguous=True):
+        return (x.shape != shape or x.dtype != dt or x.device != dev
+                or (not x.is_contiguous() if contiguous else x.stride(-1) != 1))
+    if not 1 <= W <= 8 or R % W != 0:
+        raise ValueError("beam_select: the beam width topv.shape[1] must be in [1, 8] and divide the rows")
+    if (bad(topv, (R, W), torch.float32) or bad(topi, (R, W), torch.int32) or bad(lse, (R,), torch.float32)
+            or bad(cum, (R,), torch.float32) or bad(fin, (R,), torch.uint8) or bad(tokens, (R, T), torch.int64, False)
+            or bad(pad, (R, T), torch.uint8, False) or bad(anc, (R, T), torch.int32, False)
+            or (parent is not None and bad(parent, (R,), torch.int32))):
+        raise ValueError("beam_select: topv (R, W) fp32, topi (R, W) int32, lse / cum (R,) fp32, fin (R,) uint8, tokens "
+                         "(R, T) int64, pad (R, T) uint8, anc (R, T) int32, parent (R,) int32, all on one device")
+    if _is_step(t):
+        _check_step(t, dev, "beam_select")
+    if topv.is_cuda and bool(lib().csa_beam_supported(W, T)):
+        t_dev = t if _is_step(t) else torch.tensor([int(t)], dtype=torch.int32, device=dev)
+        a = BeamSelectArgs(B=R // W, W=W, T=T, topv=_ptr(topv), topi=_ptr(topi), lse=_ptr(lse), cum=_ptr(cum),
+                           fin=_ptr(fin), tokens=_ptr(tokens), tok_stride=tokens.stride(0), pad=_ptr(pad),
+                           pad_stride=pad.stride(0), anc=_ptr(anc), anc_stride=anc.stride(0), parent=_ptr(parent),
+                           eos_id=eos, pad_id=int(pad_id), t_dev=_ptr(t_dev))
+        with on_device(dev):
+            check(lib().csa_beam_select(ctypes.byref(a), _stream(dev)), "csa_beam_select")
+    else:
+        _beam_select_ref(topv, topi, lse, cum, fin, tokens, pad, anc, _step_value(t, 0, T - 1, "beam_select"), eos,
+                         int(pad_id), parent)

@@ -258,7 +258,7 @@ class MultiheadAttention(nn.MultiheadAttention):
         w_kv, b_kv = self.in_proj_weight[E:], self.in_proj_bias[E:]
         return F.linear(memory, w_kv, b_kv).view(B, S, 2, self.num_heads, E // self.num_heads)
 
-    def step(self, x, k_cache=None, v_cache=None, t=None, memory_kv=None, key_mask=None):
+    def step(self, x, k_cache=None, v_cache=None, t=None, memory_kv=None, key_mask=None, anc=None, kv_group=1):
         """forward() for the single query position x (B, 1, E), eval mode (no dropout), need_weights=False.
 
         Self-attention (memory_kv None): the packed QKV projection of x; this position's key / value rows are
@@ -266,7 +266,10 @@ class MultiheadAttention(nn.MultiheadAttention):
         the causal row t of forward(); t is an int, or a 1-element int32 device counter that the kernel reads
         itself (the caches' row count is then the capacity). Cross-attention: the q projection alone against memory_kv =
         project_memory(memory). key_mask: (B, >= keys) or (B, H, >= keys) uint8, non-zero = masked key (a
-        key-padding mask). Inference only: the projections are plain F.linear (hipBLASLt), no autograd glue."""
+        key-padding mask). Inference only: the projections are plain F.linear (hipBLASLt), no autograd glue.
+        Beam search: anc (B, Tmax) int32 makes the self-attention read key j < t of row b from cache row anc[b, j];
+        kv_group = W makes the cross-attention read memory_kv and key_mask, which then hold B / W rows, at row
+        b // W (decode_ops.decode_attention)."""
         from .decode_ops import decode_attention
         B, _, E = x.shape
         H = self.num_heads
@@ -274,11 +277,11 @@ class MultiheadAttention(nn.MultiheadAttention):
         if memory_kv is None:
             qkv = F.linear(x, self.in_proj_weight, self.in_proj_bias).view(B, 3, H, hd)
             q, k_new, v_new = qkv.unbind(1)
-            o = decode_attention(q, k_cache, v_cache, key_mask=key_mask, k_new=k_new, v_new=v_new, t=t)
+            o = decode_attention(q, k_cache, v_cache, key_mask=key_mask, k_new=k_new, v_new=v_new, t=t, anc=anc)
         else:
             q = F.linear(x, self.in_proj_weight[:E], self.in_proj_bias[:E]).view(B, H, hd)
             k, v = (u.transpose(1, 2) for u in memory_kv.unbind(2))  # (B, H, S, hd) views
-            o = decode_attention(q, k, v, key_mask=key_mask)
+            o = decode_attention(q, k, v, key_mask=key_mask, kv_group=kv_group)
         return F.linear(o, self.out_proj.weight, self.out_proj.bias).view(B, 1, E)
 
 

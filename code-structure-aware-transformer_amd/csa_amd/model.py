@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .data import BOS, UNK
+from .data import BOS, EOS, UNK
 from .glue import LayerNorm, Linear, MultiheadAttention, gelu_dropout, residual_dropout
 from .module.disentangled_attn import DisentangledAttn
 from .module.sbm_attn import Attention
@@ -231,8 +231,10 @@ class DecoderLayer(nn.Module):
         """forward() in eval mode for the single position t (an int, or the device counter), x (B, 1, E):
         x + sublayer(norm(x)) three times against layer i's slots of a DecodeCache."""
         sl = self.sublayer
-        x = x + self.self_attn.step(sl[0].norm(x), cache.self_k[i], cache.self_v[i], t, key_mask=cache.self_mask)
-        x = x + self.multihead_attn.step(sl[1].norm(x), memory_kv=cache.memory_kv[i], key_mask=cache.memory_mask)
+        x = x + self.self_attn.step(sl[0].norm(x), cache.self_k[i], cache.self_v[i], t, key_mask=cache.self_mask,
+                                    anc=cache.anc)
+        x = x + self.multihead_attn.step(sl[1].norm(x), memory_kv=cache.memory_kv[i], key_mask=cache.memory_mask,
+                                         kv_group=cache.kv_group)
         return x + self.feed_forward(sl[2].norm(x))[0]
 
 
@@ -247,11 +249,17 @@ class DecodeCache:
     head_pad         None, or (B, H, max_len) uint8: the per-head key mask of the reference's decode()
                      (base_seq2seq.py:99-114). It hands nn.MultiheadAttention `tgt_mask.repeat(num_heads, 1, 1)`,
                      which that module reads as (B, H, T, T): head h of sample b sees the PAD columns of sample
-                     (b * H + h) % B. BaseDecoder.step copies column t of pad into this layout before step t."""
+                     (b * H + h) % B. BaseDecoder.step copies column t of pad into this layout before step t.
+    Beam search (make_cache(..., beam=W)): self_k / self_v and pad hold R = B * W hypothesis rows while memory_kv and
+    memory_mask keep B rows, shared by the kv_group = W rows of an AST, and
+    anc              (R, max_len) int32: anc[r, j] = the self_k / self_v row that holds key j of hypothesis r. A
+                     hypothesis' history stays where its ancestors stored it; beam_select rewrites this table, never
+                     the cache."""
 
-    def __init__(self, self_k, self_v, memory_kv, memory_mask, pad, head_pad=None):
+    def __init__(self, self_k, self_v, memory_kv, memory_mask, pad, head_pad=None, anc=None, kv_group=1):
         self.self_k, self.self_v, self.memory_kv = self_k, self_v, memory_kv
         self.memory_mask, self.pad, self.head_pad = memory_mask, pad, head_pad
+        self.anc, self.kv_group = anc, kv_group
 
     @property
     def self_mask(self):
@@ -271,18 +279,25 @@ class BaseDecoder(nn.Module):
             out, w = mod(out, memory, tgt_mask=tgt_mask, memory_key_padding_mask=memory_key_padding_mask)
         return (self.norm(out) if self.norm is not None else out), w
 
-    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False):
+    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False, beam=None):
         """DecodeCache for a batch-first memory (B, S, E) and up to max_len target positions. repeat_heads: key-pad
         the heads as forward() does when given make_std_mask(...).repeat(num_heads, 1, 1), the reference's decode();
-        otherwise head h of sample b sees sample b's PAD columns (a (B*H, T, T) mask built by repeat_interleave)."""
+        otherwise head h of sample b sees sample b's PAD columns (a (B*H, T, T) mask built by repeat_interleave).
+        beam=W: the cache of a beam search of width W, R = B * W self-attention rows, pad rows and ancestry rows over
+        the B memory rows and the (B, S) memory mask (not with repeat_heads: see DecodeCache)."""
         B, _, E = memory.shape
         H = self.layers[0].self_attn.num_heads
-        kv = [torch.zeros(2, B, H, max_len, E // H, device=memory.device, dtype=memory.dtype) for _ in self.layers]
+        if beam is not None and (repeat_heads or beam < 1):
+            raise ValueError("make_cache: beam is a positive width and does not go with repeat_heads")
+        R = B if beam is None else B * beam
+        kv = [torch.zeros(2, R, H, max_len, E // H, device=memory.device, dtype=memory.dtype) for _ in self.layers]
         mm = None if memory_key_padding_mask is None else memory_key_padding_mask.to(torch.uint8).contiguous()
-        pad = torch.zeros(B, max_len, dtype=torch.uint8, device=memory.device)
+        pad = torch.zeros(R, max_len, dtype=torch.uint8, device=memory.device)
         head_pad = torch.zeros(B, H, max_len, dtype=torch.uint8, device=memory.device) if repeat_heads else None
+        anc = None if beam is None else torch.zeros(R, max_len, dtype=torch.int32, device=memory.device)
         return DecodeCache([c[0] for c in kv], [c[1] for c in kv],
-                           [mod.multihead_attn.project_memory(memory) for mod in self.layers], mm, pad, head_pad)
+                           [mod.multihead_attn.project_memory(memory) for mod in self.layers], mm, pad, head_pad,
+                           anc, 1 if beam is None else beam)
 
     def step(self, x, cache, t):
         """forward() in eval mode for the single target position t: x (B, 1, E) batch-first -> (B, 1, E), equal to
@@ -553,6 +568,188 @@ class CachedGreedyGenerator(GreedyGenerator):
                 logps.append(e.logp.clone())
         out = e.ys[:, 1:].clone()
         return (out, torch.stack(logps)) if return_logp else out
+
+
+class BeamSearchGenerator(nn.Module):
+    """Beam search of width W = beam_size over the KV-cached, device-stepped decode step (no counterpart in the
+    reference, whose only strategy is GreedyGenerator).
+
+    Rows are R = B * W hypotheses, row r = b * W + w. All max_tgt_len - 1 steps run (no early stop, static shapes).
+    cum (fp32) starts at 0 for row b * W and -inf for the other W - 1 rows, all tokens BOS. Per step the eval-mode
+    generator logits z give logp = z - lse (fp32) and a candidate scores cum[r] + (z - lse[r]); a hypothesis that has
+    emitted eos_id is finished (None: never), offers the single candidate (cum, PAD), and its row still runs through
+    the decoder, ignored. Per AST the best W candidates survive: score descending, then parent row, then token.
+    The self-attention key mask is the hypothesis' own PAD columns (make_std_mask per row, DecodeCache without
+    repeat_heads): the reference decode()'s `.repeat(num_heads, 1, 1)` would let a finished hypothesis' padding mask
+    keys of live ones, so it is not reproduced here.
+
+    Nothing is gathered between steps: the K/V cache stays where each step stored it and the attention follows the
+    (R, T) ancestry table that the selection rewrites (decode_ops.beam_row_topk / beam_select, decode_attention's anc=
+    and kv_group=); the W hypotheses of an AST share one memory projection. The step index lives in a 4-byte device
+    counter, so the launches of a step never depend on it.
+
+    After the last step the W hypotheses of an AST are ranked by cum / len ** length_penalty, len counting tokens up
+    to and including the first EOS (max_tgt_len - 1 without one). forward returns the best ids (B, max_tgt_len - 1),
+    PAD after EOS; with return_all also the ids (B, W, max_tgt_len - 1) and scores (B, W) in rank order.
+
+    graph=True (CUDA model): as CachedGreedyGenerator, the step is captured once per (device, B, S, parameter
+    addresses) as one single-stream CUDAGraph over static buffers and replayed max_tgt_len - 1 times; bitwise the
+    eager result. `captures` counts the graphs captured. Inference only: a model in training mode raises."""
+
+    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+
+    def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False):
+        super().__init__()
+        if not 1 <= beam_size <= 8:
+            raise ValueError("BeamSearchGenerator: beam_size must be in [1, 8]")
+        if max_tgt_len < 2:
+            raise ValueError("BeamSearchGenerator: max_tgt_len must be at least 2")
+        self.model = model.module if multi_gpu else model
+        self.max_tgt_len = max_tgt_len
+        self.beam_size = beam_size
+        self.length_penalty = float(length_penalty)
+        self.eos_id = eos_id
+        self.start_pos = BOS
+        self.graph = graph
+        self.captures = 0
+        self._graphs = {}
+
+    def forward(self, data, return_all=False):
+        m = self.model
+        self._check_eval()
+        with torch.no_grad():
+            m.process_data(data)
+            enc, _, _, _, _ = m.encode(data)
+            return self.search(enc, data.src_mask, return_all)
+
+    def search(self, enc, src_mask=None, return_all=False):
+        """The decoder side alone: enc (B, S, E) batch-first memory (any source, CPU included), src_mask (B, S) bool
+        key-padding mask or None."""
+        self._check_eval()
+        V = self.model.generator.linear.weight.shape[0]
+        if V < self.beam_size:
+            raise ValueError("BeamSearchGenerator: the target vocabulary is smaller than the beam")
+        with torch.no_grad():
+            if self.graph and enc.is_cuda:
+                e = self._graph_state(enc, src_mask)
+                for _ in range(self.max_tgt_len - 1):
+                    e.graph.replay()
+            else:
+                cache = self.model.decoder.make_cache(enc, src_mask, self.max_tgt_len, beam=self.beam_size)
+                e = self._state(cache)
+                self._reset(e)
+                for _ in range(self.max_tgt_len - 1):
+                    self._device_step(e)
+            return self._rank(e, enc.size(0), return_all)
+
+    def _check_eval(self):
+        if self.model.training:
+            raise RuntimeError("BeamSearchGenerator: inference only (the model is in training mode)")
+
+    def _state(self, cache):
+        """The per-hypothesis state beside the cache: tokens, cumulative log-probability, finished flag, the step
+        counter and the row top-W buffers."""
+        R, T, W, dev = cache.pad.shape[0], self.max_tgt_len, self.beam_size, cache.pad.device
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
+        return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), cum=z(R, dtype=torch.float32),
+                               fin=z(R, dtype=torch.uint8), t_dev=z(1, dtype=torch.int32),
+                               lse=z(R, dtype=torch.float32), topv=z(R, W, dtype=torch.float32),
+                               topi=z(R, W, dtype=torch.int32))
+
+    def _reset(self, e):
+        """Step 0 of a new batch: BOS everywhere, one live hypothesis per AST. The self-attention cache needs no
+        reset (rows above t are never read); the ancestry table is cleared so that every entry stays a valid row."""
+        e.ys.zero_()
+        e.ys[:, 0] = self.start_pos
+        e.cache.pad.zero_()
+        e.cache.anc.zero_()
+        e.cum.fill_(float("-inf"))
+        e.cum.view(-1, self.beam_size)[:, 0] = 0.0
+        e.fin.zero_()
+        e.t_dev.zero_()
+
+    def _device_step(self, e):
+        """One beam step with every step-dependent index read from e.t_dev (on the device where the kernels run): the
+        same launches for every t. Ends by advancing the counter, after its last reader."""
+        from .decode_ops import beam_row_topk, beam_select
+        m, T = self.model, self.max_tgt_len
+        x = m.tgt_embedding.step(e.ys, e.t_dev)
+        dec = m.decoder.step(x, e.cache, e.t_dev)
+        logits = m.generator.linear(dec[:, 0])
+        beam_row_topk(logits, self.beam_size, e.lse, e.topv, e.topi, t_dev=e.t_dev, t_end=T - 1)
+        beam_select(e.topv, e.topi, e.lse, e.cum, e.fin, e.ys, e.cache.pad, e.cache.anc, e.t_dev, eos_id=self.eos_id,
+                    pad_id=PAD)
+        e.t_dev.add_(1)
+
+    def _rank(self, e, B, return_all):
+        W, T = self.beam_size, self.max_tgt_len
+        ids = e.ys[:, 1:]
+        length = torch.full((B * W,), T - 1, dtype=torch.long, device=ids.device)
+        if self.eos_id is not None:
+            is_eos = ids == self.eos_id
+            length = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, length)
+        score = e.cum.clone() if self.length_penalty == 0.0 else e.cum / length.float() ** self.length_penalty
+        score = score.view(B, W)
+        order = torch.argsort(score, dim=1, descending=True, stable=True)
+        ranked = ids.reshape(B, W, T - 1).gather(1, order[:, :, None].expand(B, W, T - 1))
+        best = ranked[:, 0].clone()
+        return (best, ranked, score.gather(1, order)) if return_all else best
+
+    # ---- graph=True: one captured HIP graph of the device-stepped beam step, replayed max_tgt_len - 1 times ----
+
+    def _step_params(self):
+        m = self.model
+        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
+        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
+
+    def _capture(self, enc, S):
+        from ._lib import lib
+        m = self.model
+        dev, B, T, W = enc.device, enc.size(0), self.max_tgt_len, self.beam_size
+        E, H = enc.size(2), m.decoder.layers[0].self_attn.num_heads
+        if not lib().csa_beam_supported(W, T) or enc.dtype != torch.float32:
+            raise ValueError("BeamSearchGenerator: graph=True needs fp32 and max_tgt_len <= 256 (csa_beam_supported)")
+        R = B * W
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
+        kv = [z(2, R, H, T, E // H, dtype=enc.dtype) for _ in m.decoder.layers]
+        cache = DecodeCache([c[0] for c in kv], [c[1] for c in kv],
+                            [z(B, S, 2, H, E // H, dtype=enc.dtype) for _ in m.decoder.layers],
+                            z(B, S, dtype=torch.uint8), z(R, T, dtype=torch.uint8), None, z(R, T, dtype=torch.int32), W)
+        e = self._state(cache)
+        self._reset(e)
+        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
+        # are then in place and stay outside the capture
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._device_step(e)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        e.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
+            self._device_step(e)
+        self.captures += 1
+        return e
+
+    def _graph_state(self, enc, src_mask):
+        m = self.model
+        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
+        # reallocated parameters recapture; weights updated in place are simply read by the next replay
+        key = (enc.device, B, S, T, self.beam_size, tuple(p.data_ptr() for p in self._step_params()))
+        e = self._graphs.get(key)
+        if e is None:
+            with torch.cuda.device(enc.device):
+                e = self._capture(enc, S)
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                del self._graphs[next(iter(self._graphs))]
+            self._graphs[key] = e
+        for kv, mod in zip(e.cache.memory_kv, m.decoder.layers):
+            kv.copy_(mod.multihead_attn.project_memory(enc))
+        if src_mask is None:
+            e.cache.memory_mask.zero_()
+        else:
+            e.cache.memory_mask.copy_(src_mask)
+        self._reset(e)
+        return e
 
 
 class _GatherTargets(torch.autograd.Function):

@@ -14,6 +14,14 @@
 //                       forward's row function (csa_ln_row.hpp): bitwise the gather + add + csa_layernorm_fwd
 // A counter outside its range makes the launch store nothing and read no row.
 //
+// Beam search (csa_decode_attn_beam) is the same kernel with BEAM = true, two uniform changes of addressing only:
+//   ancestry  (anc set, self-attention) key / value j < t of row r is read from cache row anc[r, j]: a hypothesis'
+//             history stays where its ancestors stored it and no cache row is ever moved; row (r, t) is stored as above;
+//   kv_group  (cross-attention) K, V and the mask are read at batch index r / kv_group: the hypotheses of an AST
+//             share one memory projection.
+// The chunk walk, the online softmax and the P.V order are the ones below, so for a cache that really was gathered
+// the two instantiations agree bitwise.
+//
 // M = 1, so there is no matrix product to feed an MFMA: both kernels are bound by memory latency (a few
 // hundred KB to a few tens of MB per launch) and are written for wave64 with 16-byte global loads.
 //
@@ -56,6 +64,9 @@ struct DecArgs {
   const uint8_t* mask; int64_t mask_sb, mask_sh;
   float scale;
   float* out;
+  // BEAM only
+  const int32_t* anc; int64_t anc_s;  // (B, >= len) cache row of key j of row b, or null
+  int kv_group, B;                    // K / V / mask batch index = b / kv_group
 };
 
 __device__ __forceinline__ float wave_max(float v) {
@@ -69,6 +80,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The cache row that holds key j of this hypothesis, clamped into [0, B): a bad table reads a wrong row, never
+// outside the cache.
+__device__ __forceinline__ int64_t anc_row(const int32_t* __restrict__ arow, int j, int B) {
+  const int r = arow[j];
+  return r < 0 ? 0 : (r >= B ? B - 1 : r);
+}
+
+template <bool BEAM>
 __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a) {
   __shared__ f32x4 qs[DEC_WAVES][DEC_MAX_HD / 4];
   __shared__ float ps[DEC_WAVES][64];
@@ -89,12 +108,14 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
   const int KG = 64 / DC;     // key groups of the P.V phase (>= 2)
   const bool append = t >= 0;
 
+  const int bk = BEAM ? b / a.kv_group : b;  // the batch index of K, V and the mask
+  const int32_t* arow = (BEAM && a.anc) ? a.anc + b * a.anc_s : nullptr;
   const float* qrow = a.q + b * a.q_sb + h * a.q_sh;
-  float* Kb = a.K + b * a.k_sb + h * a.k_sh;
-  float* Vb = a.V + b * a.v_sb + h * a.v_sh;
+  float* Kb = a.K + bk * a.k_sb + h * a.k_sh;
+  float* Vb = a.V + bk * a.v_sb + h * a.v_sh;
   const float* knew = append ? a.k_new + b * a.kn_sb + h * a.kn_sh : nullptr;
   const float* vnew = append ? a.v_new + b * a.vn_sb + h * a.vn_sh : nullptr;
-  const uint8_t* mrow = a.mask ? a.mask + b * a.mask_sb + h * a.mask_sh : nullptr;
+  const uint8_t* mrow = a.mask ? a.mask + bk * a.mask_sb + h * a.mask_sh : nullptr;
 
   if (lane < DC) {
     qs[w][lane] = reinterpret_cast<const f32x4*>(qrow)[lane];
@@ -116,6 +137,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
     const bool in = j < len;
     const int jc = in ? j : len - 1;  // always a readable row; the value is dropped below
     const float* krow = (append && jc == t) ? knew : Kb + (int64_t)jc * a.k_sn;
+    if (BEAM && arow && jc != t) krow = a.K + anc_row(arow, jc, a.B) * a.k_sb + h * a.k_sh + (int64_t)jc * a.k_sn;
     float s = 0.f;
 #pragma unroll 8
     for (int c = 0; c < DC; ++c) {
@@ -159,6 +181,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
             const int jl = ok ? ju : jj;
             const int jk = j0 + jl;
             const float* vrow = (append && jk == t) ? vnew : Vb + (int64_t)jk * a.v_sn;
+            if (BEAM && arow && jk != t) vrow = a.V + anc_row(arow, jk, a.B) * a.v_sb + h * a.v_sh + (int64_t)jk * a.v_sn;
             const f32x4 x = reinterpret_cast<const f32x4*>(vrow)[dc];
             pj[u] = ok ? ps[w][jl] : 0.f;
 #pragma unroll
@@ -311,8 +334,10 @@ inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 inline bool m4(int64_t s) { return s % 4 == 0; }
 
 // csa_decode_attn (step == false: host t, len = key count) and csa_decode_attn_step (step == true: t read from
-// t_dev by the kernel, len = the capacity of K / V / mask): one validation, one kernel.
-csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool step, const int32_t* t_dev, void* stream) {
+// t_dev by the kernel, len = the capacity of K / V / mask): one validation, one kernel. csa_decode_attn_beam
+// (beam == true) is either of them, by t_dev, on the BEAM instantiation with its ancestry table and group.
+csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool step, const int32_t* t_dev, void* stream,
+                            bool beam = false, const int32_t* anc = nullptr, int64_t anc_stride = 0, int64_t kv_group = 1) {
   const auto fail = [fn](csa_status s, const char* m) {
     csa::set_error("%s: %s", fn, m);
     return s;
@@ -328,6 +353,14 @@ csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool 
     if (!t_dev || (((uintptr_t)t_dev) & 3)) return fail(CSA_INVALID_ARG, "t_dev must be a 4-byte aligned device pointer");
   } else if (append && (a->t < 0 || a->t + 1 != a->len)) {
     return fail(CSA_INVALID_ARG, "append mode needs len == t + 1");
+  }
+  if (beam) {
+    if (kv_group < 1 || kv_group > 0x7fffffff || a->B % kv_group != 0)
+      return fail(CSA_INVALID_ARG, "kv_group must be positive and divide the row count B");
+    if (anc && (kv_group != 1 || !append))
+      return fail(CSA_INVALID_ARG, "an ancestry table goes with append mode and kv_group == 1");
+    if (anc && ((((uintptr_t)anc) & 3) || anc_stride < a->len))
+      return fail(CSA_INVALID_ARG, "anc must be 4-byte aligned with a row stride >= len");
   }
   if (a->B == 0) return CSA_OK;
   if (!a->q || !a->K || !a->V || !a->out) return fail(CSA_INVALID_ARG, "null pointer");
@@ -347,9 +380,14 @@ csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool 
   d.mask = a->mask; d.mask_sb = a->mask_sb; d.mask_sh = a->mask_sh;
   d.scale = a->scale;
   d.out = a->out;
+  d.anc = anc; d.anc_s = anc_stride; d.kv_group = (int)kv_group; d.B = (int)a->B;
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
-  hipLaunchKernelGGL(k_decode_attn, dim3((unsigned)((d.BH + DEC_WAVES - 1) / DEC_WAVES)), dim3(64 * DEC_WAVES), 0, st, d);
+  const dim3 grid((unsigned)((d.BH + DEC_WAVES - 1) / DEC_WAVES));
+  if (beam)
+    hipLaunchKernelGGL(k_decode_attn<true>, grid, dim3(64 * DEC_WAVES), 0, st, d);
+  else
+    hipLaunchKernelGGL(k_decode_attn<false>, grid, dim3(64 * DEC_WAVES), 0, st, d);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     csa::set_error("%s: %s", fn, hipGetErrorString(e));
@@ -370,6 +408,11 @@ csa_status csa_decode_attn(const csa_decode_attn_args* a, void* stream) {
 
 csa_status csa_decode_attn_step(const csa_decode_attn_args* a, const int32_t* t_dev, void* stream) {
   return decode_attn_impl("csa_decode_attn_step", a, true, t_dev, stream);
+}
+
+csa_status csa_decode_attn_beam(const csa_decode_attn_args* a, const int32_t* t_dev, const int32_t* anc,
+                                int64_t anc_stride, int64_t kv_group, void* stream) {
+  return decode_attn_impl("csa_decode_attn_beam", a, t_dev != nullptr, t_dev, stream, true, anc, anc_stride, kv_group);
 }
 
 csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int64_t T, const int32_t* t_dev,

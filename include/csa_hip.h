@@ -19,6 +19,10 @@
  *   csa_decode_attn / csa_argmax_rows  module/base_seq2seq.py:117-145 GreedyGenerator, one KV-cached decode step
  *                      (and their device-stepped forms for a captured step: csa_decode_attn_step, csa_decode_embed,
  *                      csa_argmax_rows_step)
+ *   csa_beam_row_topk / csa_beam_select / csa_decode_attn_beam  beam search over the same cached step (no
+ *                      counterpart in the reference, whose only strategy is the greedy loop above): per-row top-W
+ *                      and log-sum-exp, the per-AST merge with its in-place state update, and the decode attention
+ *                      reading its cache through an ancestry table and one memory projection per AST
  *
  * Conventions (all entry points):
  *   - fp32 data; device pointers; sizes and strides are int64 ELEMENT counts; the last
@@ -325,6 +329,51 @@ csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int
 csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
                                 uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
                                 const int32_t* t_dev, void* stream);
+
+/* ---- v10 additions: beam search over the device-stepped decode step ----
+ * Rows are R = B * W hypotheses, row r = b * W + w of AST b, beam width 1 <= W <= 8; the token buffer has T columns,
+ * 2 <= T <= 256 (csa_beam_supported states both limits). All fp32, deterministic (fixed reduction orders, no float
+ * atomics), no allocation, no sync. Each reads the step t from t_dev as above; a t outside the stated range makes
+ * the launch store nothing and read no row, so one captured graph serves every step.
+ *
+ * csa_beam_row_topk: for each row of z (rows, V) contiguous, V >= W: lse[r] = m + log sum exp(z - m) (an all -inf row
+ * gives -inf), topv[r, 0..W) = the W largest logits in descending order and topi[r, 0..W) their indices, the lowest
+ * index first among equal values (-inf entries included: an all -inf row gives 0 .. W-1). t_dev may be NULL (the
+ * launch is then unconditional); otherwise valid t: [0, t_end). */
+int csa_beam_supported(int64_t W, int64_t T);
+csa_status csa_beam_row_topk(const float* z, int64_t rows, int64_t V, int64_t W, float* lse, float* topv, int32_t* topi,
+                             const int32_t* t_dev, int64_t t_end, void* stream);
+/* csa_beam_select: one beam step of every AST, in place. Candidates of AST b: for a live row r (fin[r] == 0) the W
+ * pairs (cum[r] + (topv[r, k] - lse[r]), topi[r, k]); for a finished row the single pair (cum[r], pad_id). A score
+ * that is -inf or NaN counts as -inf. The best W (score descending, then parent row ascending, then token ascending)
+ * become rows b*W + 0 .. b*W + W-1: child c of parent p takes columns 0..t of p's tokens and pad rows and 0..t-1 of
+ * its anc row, then tokens[c, t+1] = token, pad[c, t+1] = (token == pad_id), anc[c, t] = p (the cache row where key
+ * t of c's history was stored), cum[c] = score, fin[c] = fin[p] || token == eos_id (eos_id < 0: never), and, when
+ * parent is given, parent[c] = p. All reads of an AST's rows precede all writes. Valid t: [0, T - 1). */
+typedef struct csa_beam_select_args {
+  int64_t B, W, T;
+  const float* topv; const int32_t* topi;     /* (B*W, W) contiguous, from csa_beam_row_topk */
+  const float* lse;                           /* (B*W) */
+  float* cum; uint8_t* fin;                   /* (B*W) in / out */
+  int64_t* tokens; int64_t tok_stride;        /* (B*W, T) in / out, row strides >= T */
+  uint8_t* pad; int64_t pad_stride;           /* (B*W, T) in / out: the self-attention key mask */
+  int32_t* anc; int64_t anc_stride;           /* (B*W, T) in / out: the ancestry table of csa_decode_attn_beam */
+  int32_t* parent;                            /* (B*W) out, or NULL */
+  int64_t eos_id, pad_id;
+  const int32_t* t_dev;
+} csa_beam_select_args;
+csa_status csa_beam_select(const csa_beam_select_args* a, void* stream);
+/* csa_decode_attn_beam: csa_decode_attn (t_dev NULL) or csa_decode_attn_step (t_dev set) over a->B = R rows with
+ * beam addressing; the chunk walk, the softmax and the summation order are theirs, so on a cache that really was
+ * gathered the results are bitwise equal.
+ * Self-attention (anc set; append mode and kv_group == 1 required): key / value j < t of row r is read from cache row
+ * anc[r * anc_stride + j] (clamped into [0, R)), key t from k_new / v_new, which are stored at cache row r, position
+ * t, as without a table; the mask byte is mask[r, j]. No cache row is moved. anc_stride >= len.
+ * Cross-attention (anc NULL): K, V and the mask are read at batch index r / kv_group, so the kv_group hypotheses of
+ * an AST share one (R / kv_group, S, 2, H, hd) projection; R % kv_group == 0.
+ * Otherwise validated as csa_decode_attn (alignment, strides multiples of 4 elements). */
+csa_status csa_decode_attn_beam(const csa_decode_attn_args* a, const int32_t* t_dev, const int32_t* anc,
+                                int64_t anc_stride, int64_t kv_group, void* stream);
 
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
