@@ -34,9 +34,23 @@ def _is_step(t):
     return isinstance(t, torch.Tensor)
 
 
+def _rows_hip_ok(x):
+    """fp32 CUDA contiguous rows (at least one column): what the row kernels (argmax, top-W) take."""
+    return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] >= 1
+
+
 def _check_step(t, device, what):
     if t.dtype != torch.int32 or t.numel() != 1 or t.device != device:
         raise ValueError(f"{what}: the device step must be a 1-element int32 tensor on the tensors' device")
+
+
+def _step_value(t, lo, hi, what):
+    """The host-side value of a step given as an int or a counter tensor (fallback paths only: reading the counter
+    is not for a captured graph)."""
+    tt = int(t.item()) if _is_step(t) else int(t)
+    if not lo <= tt < hi:
+        raise ValueError(f"{what}: step {tt} outside [{lo}, {hi})")
+    return tt
 
 
 def _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None, anc=None, kv_group=1):
@@ -68,10 +82,8 @@ def _decode_attention_hip(q, K, V, length, key_mask, k_new, v_new, t, scale, out
 
 def _decode_attention_ref(q, K, V, length, key_mask, k_new, v_new, t, scale, out=None, anc=None, kv_group=1):
     B, H, hd = q.shape
-    if _is_step(t):  # the host reads the counter: not for a captured graph
-        t, cap = int(t.item()), length
-        if not 0 <= t < cap:
-            raise ValueError(f"decode_attention: step {t} outside the capacity {cap}")
+    if _is_step(t):  # length is the capacity
+        t = _step_value(t, 0, length, "decode_attention")
         length = t + 1
     if k_new is not None:
         K[:, :, t] = k_new
@@ -192,16 +204,14 @@ def _argmax_rows_step(x, ys, pad, pad_id, t_dev, head_pad):
         raise ValueError("argmax_rows: with t_dev, out is the (rows, T) int64 token buffer, is_pad (rows, T) uint8, both "
                          "with a contiguous last dim, and head_pad (rows, H, T) uint8 contiguous")
     _check_step(t_dev, x.device, "argmax_rows")
-    if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and V >= 1:
+    if _rows_hip_ok(x):
         with on_device(x.device):
             check(lib().csa_argmax_rows_step(_ptr(x), rows, V, _ptr(ys), ys.stride(0), T, _ptr(pad),
                                              pad.stride(0) if pad is not None else 0, _ptr(head_pad),
                                              head_pad.shape[1] if head_pad is not None else 0, pad_id, _ptr(t_dev),
                                              _stream(x.device)), "csa_argmax_rows_step")
         return ys
-    col = int(t_dev.item()) + 1  # the host reads the counter: not for a captured graph
-    if not 1 <= col < T:
-        raise ValueError(f"argmax_rows: column {col} outside [1, {T})")
+    col = _step_value(t_dev, 0, T - 1, "argmax_rows") + 1  # column in [1, T)
     _argmax_rows_ref(x, ys[:, col], None if pad is None else pad[:, col], pad_id, None)
     if head_pad is not None:
         _head_view(head_pad, rows)[:, :, col] = ys[:, col] == pad_id
@@ -222,14 +232,14 @@ def argmax_rows(x, out=None, is_pad=None, pad_id=0, maxval=None, t_dev=None, hea
         return _argmax_rows_step(x, out, is_pad, pad_id, t_dev, head_pad)
     if head_pad is not None:
         raise ValueError("argmax_rows: head_pad goes with t_dev")
-    rows, V = x.shape
+    rows, _ = x.shape
     if out is None:
         out = torch.empty(rows, dtype=torch.int64, device=x.device)
     if out.dtype != torch.int64 or out.shape != (rows,) or (is_pad is not None and (
             is_pad.dtype != torch.uint8 or is_pad.shape != (rows,))) or (maxval is not None and (
             maxval.dtype != torch.float32 or maxval.shape != (rows,) or not maxval.is_contiguous())):
         raise ValueError("argmax_rows: out (rows,) int64, is_pad (rows,) uint8, maxval (rows,) fp32 contiguous")
-    if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and V >= 1:
+    if _rows_hip_ok(x):
         _argmax_rows_hip(x, out, is_pad, pad_id, maxval)
     else:
         _argmax_rows_ref(x, out, is_pad, pad_id, maxval)
@@ -261,21 +271,11 @@ def decode_embed(ys, t, emb):
                                          pe.shape[0] if pe is not None else 0, _ptr(norm.weight), _ptr(norm.bias),
                                          float(norm.eps), _ptr(x), E, _stream(ys.device)), "csa_decode_embed")
         return x
-    tt = int(t.item())  # the host reads the counter: not for a captured graph
-    if not 0 <= tt < T:
-        raise ValueError(f"decode_embed: step {tt} outside [0, {T})")
+    tt = _step_value(t, 0, T, "decode_embed")
     return emb.step(ys[:, tt:tt + 1], tt)[:, 0]
 
 
 # ---- beam search: per-row top-W and log-sum-exp, per-AST merge with the in-place state update ----
-
-def _step_value(t, lo, hi, what):
-    """The host-side value of a step given as an int or a counter tensor (fallback paths only)."""
-    tt = int(t.item()) if _is_step(t) else int(t)
-    if not lo <= tt < hi:
-        raise ValueError(f"{what}: step {tt} outside [{lo}, {hi})")
-    return tt
-
 
 def _beam_row_topk_ref(z, W, lse, topv, topi):
     zf = z.float()
@@ -309,7 +309,7 @@ def beam_row_topk(z, W, lse=None, topv=None, topi=None, t_dev=None, t_end=None):
         if x.shape != shape or x.dtype != dt or x.device != z.device or not x.is_contiguous():
             raise ValueError("beam_row_topk: lse (rows,) fp32, topv (rows, W) fp32, topi (rows, W) int32, contiguous, "
                              "on z's device")
-    if z.is_cuda and z.dtype == torch.float32 and z.is_contiguous():
+    if _rows_hip_ok(z):
         with on_device(z.device):
             check(lib().csa_beam_row_topk(_ptr(z), rows, V, W, _ptr(lse), _ptr(topv), _ptr(topi), _ptr(t_dev),
                                           0 if t_end is None else int(t_end), _stream(z.device)), "csa_beam_row_topk")

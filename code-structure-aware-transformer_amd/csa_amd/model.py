@@ -239,7 +239,7 @@ class DecoderLayer(nn.Module):
 
 
 class DecodeCache:
-    """What incremental decoding keeps between steps, owned by the caller (BaseDecoder.make_cache):
+    """What incremental decoding keeps between steps, owned by the caller (BaseDecoder.empty_cache, make_cache):
     self_k / self_v  per layer (B, H, max_len, hd): the self-attention keys / values of positions decoded so far;
     memory_kv        per layer (B, S, 2, H, hd): the cross-attention projection of the encoder memory;
     memory_mask      (B, S) uint8 source key-padding mask (non-zero = PAD) or None;
@@ -279,25 +279,47 @@ class BaseDecoder(nn.Module):
             out, w = mod(out, memory, tgt_mask=tgt_mask, memory_key_padding_mask=memory_key_padding_mask)
         return (self.norm(out) if self.norm is not None else out), w
 
-    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False, beam=None):
-        """DecodeCache for a batch-first memory (B, S, E) and up to max_len target positions. repeat_heads: key-pad
-        the heads as forward() does when given make_std_mask(...).repeat(num_heads, 1, 1), the reference's decode();
-        otherwise head h of sample b sees sample b's PAD columns (a (B*H, T, T) mask built by repeat_interleave).
-        beam=W: the cache of a beam search of width W, R = B * W self-attention rows, pad rows and ancestry rows over
-        the B memory rows and the (B, S) memory mask (not with repeat_heads: see DecodeCache)."""
-        B, _, E = memory.shape
-        H = self.layers[0].self_attn.num_heads
+    def empty_cache(self, B, max_len, device, dtype, repeat_heads=False, beam=None, S=None):
+        """A zeroed DecodeCache for B memory rows and up to max_len target positions: the one place that spells the
+        layout (see DecodeCache). repeat_heads: key-pad the heads as forward() does when given
+        make_std_mask(...).repeat(num_heads, 1, 1), the reference's decode(); otherwise head h of sample b sees sample
+        b's PAD columns (a (B*H, T, T) mask built by repeat_interleave). beam=W: the cache of a beam search of width W,
+        R = B * W self-attention rows, pad rows and ancestry rows over the B memory rows and the (B, S) memory mask (not
+        with repeat_heads). S: also static memory_kv / memory_mask buffers for S source keys, which load_memory fills
+        in place (a captured graph keeps reading them); without S the memory side is left to the caller."""
+        attn = self.layers[0].self_attn
+        H, hd = attn.num_heads, attn.embed_dim // attn.num_heads
         if beam is not None and (repeat_heads or beam < 1):
             raise ValueError("make_cache: beam is a positive width and does not go with repeat_heads")
         R = B if beam is None else B * beam
-        kv = [torch.zeros(2, R, H, max_len, E // H, device=memory.device, dtype=memory.dtype) for _ in self.layers]
-        mm = None if memory_key_padding_mask is None else memory_key_padding_mask.to(torch.uint8).contiguous()
-        pad = torch.zeros(R, max_len, dtype=torch.uint8, device=memory.device)
-        head_pad = torch.zeros(B, H, max_len, dtype=torch.uint8, device=memory.device) if repeat_heads else None
-        anc = None if beam is None else torch.zeros(R, max_len, dtype=torch.int32, device=memory.device)
-        return DecodeCache([c[0] for c in kv], [c[1] for c in kv],
-                           [mod.multihead_attn.project_memory(memory) for mod in self.layers], mm, pad, head_pad,
-                           anc, 1 if beam is None else beam)
+        z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
+        kv = [z(2, R, H, max_len, hd) for _ in self.layers]
+        return DecodeCache(self_k=[c[0] for c in kv], self_v=[c[1] for c in kv],
+                           memory_kv=None if S is None else [z(B, S, 2, H, hd) for _ in self.layers],
+                           memory_mask=None if S is None else z(B, S, dt=torch.uint8),
+                           pad=z(R, max_len, dt=torch.uint8),
+                           head_pad=z(B, H, max_len, dt=torch.uint8) if repeat_heads else None,
+                           anc=None if beam is None else z(R, max_len, dt=torch.int32),
+                           kv_group=1 if beam is None else beam)
+
+    def load_memory(self, cache, memory, memory_key_padding_mask):
+        """A new batch-first memory (B, S, E) into the static buffers of an empty_cache(..., S=S) cache: every layer's
+        cross-attention projection and the key-padding mask (None: no key is masked, the buffer is zeroed)."""
+        for kv, mod in zip(cache.memory_kv, self.layers):
+            kv.copy_(mod.multihead_attn.project_memory(memory))
+        if memory_key_padding_mask is None:
+            cache.memory_mask.zero_()
+        else:
+            cache.memory_mask.copy_(memory_key_padding_mask)
+
+    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False, beam=None):
+        """empty_cache for a batch-first memory (B, S, E), holding the memory projections themselves (no copy) and the
+        mask as uint8, or None without one."""
+        cache = self.empty_cache(memory.shape[0], max_len, memory.device, memory.dtype, repeat_heads, beam)
+        cache.memory_kv = [mod.multihead_attn.project_memory(memory) for mod in self.layers]
+        if memory_key_padding_mask is not None:
+            cache.memory_mask = memory_key_padding_mask.to(torch.uint8).contiguous()
+        return cache
 
     def step(self, x, cache, t):
         """forward() in eval mode for the single target position t: x (B, 1, E) batch-first -> (B, 1, E), equal to
@@ -436,7 +458,71 @@ class GreedyGenerator(nn.Module):
         return ys[:, 1:]
 
 
-class CachedGreedyGenerator(GreedyGenerator):
+class _SteppedDecoding:
+    """graph=True of CachedGreedyGenerator and BeamSearchGenerator: the device-stepped decode step (every kernel reads
+    the step from the 4-byte device counter e.t_dev, so every step issues the same launches), captured once per
+    (device, B, S, max_tgt_len, the generator's key extras, parameter addresses) as one single-stream
+    torch.cuda.CUDAGraph over static buffers and replayed max_tgt_len - 1 times per call. `captures` counts the graphs
+    captured. The generator supplies _state(cache, **kw), _reset(e), _device_step(e) and, if it must, _check_capture."""
+
+    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+
+    def _init_stepped(self, graph, **cache_options):
+        self.graph = graph
+        self.captures = 0      # graphs captured so far (graph=True on a CUDA model; 0 otherwise)
+        self._graphs = {}      # key -> SimpleNamespace of static buffers and the captured step (insertion-ordered)
+        self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
+        self._cache_options = cache_options  # what the generator asks of BaseDecoder.empty_cache
+
+    def _step_params(self):
+        m = self.model
+        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
+        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
+
+    def _check_capture(self, enc):
+        """Raises where the generator's step cannot be captured for this memory."""
+
+    def _capture(self, enc, **state_kw):
+        self._check_capture(enc)
+        dev = enc.device
+        cache = self.model.decoder.empty_cache(enc.size(0), self.max_tgt_len, dev, enc.dtype, S=enc.size(1),
+                                               **self._cache_options)
+        e = self._state(cache, **state_kw)
+        self._reset(e)
+        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
+        # are then in place and stay outside the capture
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._device_step(e)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        e.graph = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
+        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
+            self._device_step(e)
+        if self._keep_graph:
+            e.graph.instantiate()
+        self.captures += 1
+        return e
+
+    def _graph_entry(self, enc, src_mask, key_extra, **state_kw):
+        """The captured entry for this memory (captured now if there is none, the oldest evicted), its static memory
+        buffers loaded from enc and src_mask and its state reset to step 0: ready for max_tgt_len - 1 replays."""
+        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
+        # reallocated parameters recapture; weights updated in place are simply read by the next replay
+        key = (enc.device, B, S, T, *key_extra, tuple(p.data_ptr() for p in self._step_params()))
+        e = self._graphs.get(key)
+        if e is None:
+            with torch.cuda.device(enc.device):
+                e = self._capture(enc, **state_kw)
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                del self._graphs[next(iter(self._graphs))]
+            self._graphs[key] = e
+        self.model.decoder.load_memory(e.cache, enc, src_mask)
+        self._reset(e)
+        return e
+
+
+class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
     """GreedyGenerator with a key/value cache: the same tokens from one decoder pass per NEW position.
 
     The decoder is causal and the key-padding mask of positions <= j never changes as ys grows, so step t needs only
@@ -448,20 +534,14 @@ class CachedGreedyGenerator(GreedyGenerator):
     EOS), as in the reference. In training mode this defers to GreedyGenerator.
 
     graph=True (eval mode, CUDA model): the loop above is bound by the host, about 70 small launches per step issued
-    from Python. The step is instead run device-stepped (every kernel reads t from a 4-byte device counter:
-    csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step), captured once per (device, B, S, max_tgt_len,
-    return_logp, parameter addresses) as one torch.cuda.CUDAGraph over static buffers and replayed max_tgt_len - 1
-    times per call; process_data, encode (its Philox key comes from the CPU generator) and the memory projections
-    stay eager. Same ids and log-probabilities, bitwise. `captures` counts the graphs captured."""
-
-    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+    from Python. The step is instead run device-stepped (csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step)
+    and replayed from one captured graph per (..., return_logp, ...) (_SteppedDecoding); process_data, encode (its
+    Philox key comes from the CPU generator) and the memory projections stay eager. Same ids and log-probabilities,
+    bitwise."""
 
     def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False):
         super().__init__(model, max_tgt_len, multi_gpu)
-        self.graph = graph
-        self.captures = 0      # graphs captured so far (graph=True on a CUDA model; 0 otherwise)
-        self._graphs = {}      # key -> SimpleNamespace of static buffers and the captured step (insertion-ordered)
-        self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
+        self._init_stepped(graph, repeat_heads=True)  # as CSATrans.decode masks
 
     def forward(self, data, return_logp=False):
         m = self.model
@@ -490,14 +570,17 @@ class CachedGreedyGenerator(GreedyGenerator):
             out = ys[:, 1:]
             return (out, torch.stack(logps)) if return_logp else out
 
-    # ---- graph=True: one captured HIP graph of a device-stepped decode step, replayed max_tgt_len - 1 times ----
+    # ---- graph=True: the device-stepped decode step that _SteppedDecoding captures and replays ----
 
-    def _step_params(self):
-        m = self.model
-        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
-        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
+    def _state(self, cache, return_logp):
+        """The static buffers beside the cache: tokens, the step counter, and the slot where each replay leaves its
+        log-probabilities when return_logp asks for them."""
+        B, T = cache.pad.shape
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=cache.pad.device)
+        return SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None,
+                               return_logp=return_logp)
 
-    def _device_step(self, e, return_logp):
+    def _device_step(self, e):
         """One decode step with every step-dependent index read from e.t_dev on the device: the same launches for
         every t, so they can be captured once. Ends by advancing the counter, after its last reader."""
         from .decode_ops import argmax_rows
@@ -507,9 +590,8 @@ class CachedGreedyGenerator(GreedyGenerator):
         dec = m.decoder.step(x, e.cache, e.t_dev)
         logits = m.generator.linear(dec[:, 0])
         argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
-        logp = gen_log_softmax(logits, 0.0) if return_logp else None
+        e.logp = gen_log_softmax(logits, 0.0) if e.return_logp else None
         e.t_dev.add_(1)
-        return logp
 
     def _reset(self, e):
         """Step 0 of a new batch. The self-attention cache needs no reset: rows above t are never read."""
@@ -519,50 +601,11 @@ class CachedGreedyGenerator(GreedyGenerator):
         e.cache.head_pad.zero_()
         e.t_dev.zero_()
 
-    def _capture(self, enc, S, return_logp):
-        m = self.model
-        dev, B, T = enc.device, enc.size(0), self.max_tgt_len
-        E, H = enc.size(2), m.decoder.layers[0].self_attn.num_heads
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
-        kv = [z(2, B, H, T, E // H, dtype=enc.dtype) for _ in m.decoder.layers]
-        cache = DecodeCache([c[0] for c in kv], [c[1] for c in kv],
-                            [z(B, S, 2, H, E // H, dtype=enc.dtype) for _ in m.decoder.layers],
-                            z(B, S, dtype=torch.uint8), z(B, T, dtype=torch.uint8), z(B, H, T, dtype=torch.uint8))
-        e = SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None)
-        self._reset(e)
-        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
-        # are then in place and stay outside the capture
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._device_step(e, return_logp)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        e.graph = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
-            e.logp = self._device_step(e, return_logp)
-        if self._keep_graph:
-            e.graph.instantiate()
-        self.captures += 1
-        return e
-
     def _forward_graph(self, data, enc, return_logp):
-        m = self.model
-        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
-        # reallocated parameters recapture; weights updated in place are simply read by the next replay
-        key = (enc.device, B, S, T, bool(return_logp), tuple(p.data_ptr() for p in self._step_params()))
-        e = self._graphs.get(key)
-        if e is None:
-            with torch.cuda.device(enc.device):
-                e = self._capture(enc, S, return_logp)
-            while len(self._graphs) >= self.MAX_GRAPHS:
-                del self._graphs[next(iter(self._graphs))]
-            self._graphs[key] = e
-        for kv, mod in zip(e.cache.memory_kv, m.decoder.layers):
-            kv.copy_(mod.multihead_attn.project_memory(enc))
-        e.cache.memory_mask.copy_(data.src_mask)
-        self._reset(e)
+        return_logp = bool(return_logp)
+        e = self._graph_entry(enc, data.src_mask, (return_logp,), return_logp=return_logp)
         logps = []
-        for _ in range(T - 1):
+        for _ in range(self.max_tgt_len - 1):
             e.graph.replay()
             if return_logp:
                 logps.append(e.logp.clone())
@@ -570,7 +613,7 @@ class CachedGreedyGenerator(GreedyGenerator):
         return (out, torch.stack(logps)) if return_logp else out
 
 
-class BeamSearchGenerator(nn.Module):
+class BeamSearchGenerator(_SteppedDecoding, nn.Module):
     """Beam search of width W = beam_size over the KV-cached, device-stepped decode step (no counterpart in the
     reference, whose only strategy is GreedyGenerator).
 
@@ -592,11 +635,9 @@ class BeamSearchGenerator(nn.Module):
     to and including the first EOS (max_tgt_len - 1 without one). forward returns the best ids (B, max_tgt_len - 1),
     PAD after EOS; with return_all also the ids (B, W, max_tgt_len - 1) and scores (B, W) in rank order.
 
-    graph=True (CUDA model): as CachedGreedyGenerator, the step is captured once per (device, B, S, parameter
-    addresses) as one single-stream CUDAGraph over static buffers and replayed max_tgt_len - 1 times; bitwise the
-    eager result. `captures` counts the graphs captured. Inference only: a model in training mode raises."""
-
-    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+    graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
+    (..., beam_size, ...) (_SteppedDecoding); bitwise the eager result. Inference only: a model in training mode
+    raises."""
 
     def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False):
         super().__init__()
@@ -610,9 +651,7 @@ class BeamSearchGenerator(nn.Module):
         self.length_penalty = float(length_penalty)
         self.eos_id = eos_id
         self.start_pos = BOS
-        self.graph = graph
-        self.captures = 0
-        self._graphs = {}
+        self._init_stepped(graph, beam=beam_size)
 
     def forward(self, data, return_all=False):
         m = self.model
@@ -631,7 +670,7 @@ class BeamSearchGenerator(nn.Module):
             raise ValueError("BeamSearchGenerator: the target vocabulary is smaller than the beam")
         with torch.no_grad():
             if self.graph and enc.is_cuda:
-                e = self._graph_state(enc, src_mask)
+                e = self._graph_entry(enc, src_mask, (self.beam_size,))
                 for _ in range(self.max_tgt_len - 1):
                     e.graph.replay()
             else:
@@ -695,61 +734,10 @@ class BeamSearchGenerator(nn.Module):
         best = ranked[:, 0].clone()
         return (best, ranked, score.gather(1, order)) if return_all else best
 
-    # ---- graph=True: one captured HIP graph of the device-stepped beam step, replayed max_tgt_len - 1 times ----
-
-    def _step_params(self):
-        m = self.model
-        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
-        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
-
-    def _capture(self, enc, S):
+    def _check_capture(self, enc):
         from ._lib import lib
-        m = self.model
-        dev, B, T, W = enc.device, enc.size(0), self.max_tgt_len, self.beam_size
-        E, H = enc.size(2), m.decoder.layers[0].self_attn.num_heads
-        if not lib().csa_beam_supported(W, T) or enc.dtype != torch.float32:
+        if not lib().csa_beam_supported(self.beam_size, self.max_tgt_len) or enc.dtype != torch.float32:
             raise ValueError("BeamSearchGenerator: graph=True needs fp32 and max_tgt_len <= 256 (csa_beam_supported)")
-        R = B * W
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
-        kv = [z(2, R, H, T, E // H, dtype=enc.dtype) for _ in m.decoder.layers]
-        cache = DecodeCache([c[0] for c in kv], [c[1] for c in kv],
-                            [z(B, S, 2, H, E // H, dtype=enc.dtype) for _ in m.decoder.layers],
-                            z(B, S, dtype=torch.uint8), z(R, T, dtype=torch.uint8), None, z(R, T, dtype=torch.int32), W)
-        e = self._state(cache)
-        self._reset(e)
-        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
-        # are then in place and stay outside the capture
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._device_step(e)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        e.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
-            self._device_step(e)
-        self.captures += 1
-        return e
-
-    def _graph_state(self, enc, src_mask):
-        m = self.model
-        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
-        # reallocated parameters recapture; weights updated in place are simply read by the next replay
-        key = (enc.device, B, S, T, self.beam_size, tuple(p.data_ptr() for p in self._step_params()))
-        e = self._graphs.get(key)
-        if e is None:
-            with torch.cuda.device(enc.device):
-                e = self._capture(enc, S)
-            while len(self._graphs) >= self.MAX_GRAPHS:
-                del self._graphs[next(iter(self._graphs))]
-            self._graphs[key] = e
-        for kv, mod in zip(e.cache.memory_kv, m.decoder.layers):
-            kv.copy_(mod.multihead_attn.project_memory(enc))
-        if src_mask is None:
-            e.cache.memory_mask.zero_()
-        else:
-            e.cache.memory_mask.copy_(src_mask)
-        self._reset(e)
-        return e
 
 
 class _GatherTargets(torch.autograd.Function):

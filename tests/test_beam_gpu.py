@@ -277,6 +277,43 @@ def test_beam_graph_mode_is_bitwise_eager_and_resets_its_state():
         assert torch.equal(a, b)
 
 
+def test_beam_graph_generator_keeps_at_most_four_graphs():
+    """Five (B, S) shapes through one generator: the fifth capture evicts the oldest entry, which is then captured
+    again and still gives the eager result."""
+    from csa_amd.model import BeamSearchGenerator
+    m = beam_ref.stub_model().cuda()
+    gen = BeamSearchGenerator(m, 3, 2, graph=True)
+    shapes = [(3, 7), (2, 7), (1, 7), (3, 5), (2, 5)]
+    g = torch.Generator().manual_seed(11)
+    encs = [torch.randn(B, S, 32, generator=g).cuda() for B, S in shapes]
+    for enc in encs:
+        gen.search(enc)
+    assert gen.captures == 5 and len(gen._graphs) == gen.MAX_GRAPHS
+    first = gen.search(encs[0], return_all=True)  # evicted as the oldest: captured again
+    assert gen.captures == 6 and len(gen._graphs) == gen.MAX_GRAPHS
+    want = BeamSearchGenerator(m, 3, 2).search(encs[0], return_all=True)
+    for a, b in zip(first, want):
+        assert torch.equal(a, b)
+
+
+def test_beam_graph_without_a_mask_clears_the_static_mask():
+    """src_mask=None through a captured entry whose static mask still holds the previous call's padding: bitwise the
+    eager result without a mask, which is not the masked one."""
+    from csa_amd.model import BeamSearchGenerator
+    T, W = 8, 3
+    m, enc, src_mask = search_case(device="cuda")
+    eager = BeamSearchGenerator(m, T, W)
+    gen = BeamSearchGenerator(m, T, W, graph=True)
+    masked = gen.search(enc, src_mask, return_all=True)
+    got = gen.search(enc, None, return_all=True)
+    assert gen.captures == 1 and bool(src_mask.any())
+    want = eager.search(enc, None, return_all=True)
+    want_masked = eager.search(enc, src_mask, return_all=True)
+    assert not torch.equal(want_masked[2], want[2])  # the mask matters: a stale one would show in the scores
+    for a, b, c, d in zip(got, want, masked, want_masked):
+        assert torch.equal(a, b) and torch.equal(c, d)
+
+
 # seed / generator scale of the production-dim decoder, chosen on the CPU oracle alone (seeds 1..8 x two scales): the
 # run that finishes a hypothesis early, reorders its beam and beats greedy; smallest decisive gap 0.0346
 PROD_BEAM = dict(seed=5, gen_scale=4.0, eos_bias=1.0)

@@ -44,6 +44,68 @@ def test_decoder_step_matches_full_pass_teacher_forced(repeat_heads):
             np.testing.assert_allclose(y[:, 0].numpy(), full[:, t].numpy(), rtol=1e-5, atol=1e-6, err_msg=f"t={t}")
 
 
+@pytest.mark.parametrize("options", [{}, {"repeat_heads": True}, {"beam": 3}], ids=["plain", "repeat_heads", "beam3"])
+def test_empty_cache_then_load_memory_is_make_cache(options):
+    """The static cache of the captured graphs (empty_cache(S=) + load_memory) against the eager one (make_cache): the
+    same fields, shapes, dtypes and None-ness, the same memory projections and mask; no mask leaves the static mask
+    zeroed where make_cache keeps None."""
+    from beam_ref import search_case
+    m, enc, src_mask = search_case()  # E=32, H=4, two layers, B=3, S=7, a padded source row
+    dec, T = m.decoder, 3
+    B, S, _ = enc.shape
+    assert bool(src_mask.any())
+    with torch.no_grad():
+        want = dec.make_cache(enc, src_mask, T, **options)
+        got = dec.empty_cache(B, T, enc.device, enc.dtype, S=S, **options)
+        assert all(not bool(kv.any()) for kv in got.memory_kv) and not bool(got.memory_mask.any())
+        dec.load_memory(got, enc, src_mask)
+    assert vars(got).keys() == vars(want).keys()
+    assert got.kv_group == want.kv_group == options.get("beam", 1)
+    assert (got.head_pad is None) == (want.head_pad is None) == ("repeat_heads" not in options)
+    assert (got.anc is None) == (want.anc is None) == ("beam" not in options)
+    for name in ("self_k", "self_v", "memory_kv", "memory_mask", "pad", "head_pad", "anc"):
+        a, b = (v if isinstance(v, list) else [v] for v in (getattr(got, name), getattr(want, name)))
+        assert len(a) == len(b) == (2 if name in ("self_k", "self_v", "memory_kv") else 1), name
+        for x, y in zip(a, b):
+            if y is not None:
+                assert x.shape == y.shape and x.dtype == y.dtype and x.device == y.device, name
+                assert torch.equal(x, y), name
+    with torch.no_grad():
+        dec.load_memory(got, enc, None)
+        assert dec.make_cache(enc, None, T, **options).memory_mask is None
+    assert got.memory_mask.shape == (B, S) and not bool(got.memory_mask.any())
+    assert all(torch.equal(x, y) for x, y in zip(got.memory_kv, want.memory_kv))
+
+
+def test_fallbacks_refuse_a_counter_outside_its_range():
+    """Off the HIP path the host reads the device counter, and a step outside the op's range raises: one step below
+    the range and the upper bound itself, for each op that takes a counter."""
+    import beam_ref
+    from csa_amd.decode_ops import argmax_rows, beam_row_topk, decode_attention, decode_embed
+    from csa_amd.model import Embeddings
+    counter = lambda t: torch.tensor([t], dtype=torch.int32)
+    B, H, hd, cap, T, V = 2, 3, 8, 6, 5, 11
+    q, kn, vn = torch.randn(B, 3, H, hd).unbind(1)
+    K, Vc = torch.randn(2, B, H, cap, hd).unbind(0)
+    x = torch.randn(B, V)
+    ys, pad = torch.zeros(B, T, dtype=torch.long), torch.zeros(B, T, dtype=torch.uint8)
+    emb = Embeddings(32, 20, 0.1, with_pos=True).eval()
+    _, state, _ = beam_ref.select_states()[0]
+    ops = {  # op -> (call with a step, the range's upper bound)
+        "decode_attention": (lambda t: decode_attention(q, K, Vc, k_new=kn, v_new=vn, t=counter(t)), cap),
+        "argmax_rows": (lambda t: argmax_rows(x, out=ys, is_pad=pad, t_dev=counter(t)), T - 1),
+        "decode_embed": (lambda t: decode_embed(ys, counter(t), emb), T),
+        "beam_row_topk": (lambda t: beam_row_topk(x, 4, t_dev=counter(t), t_end=T - 1), T - 1),
+        "beam_select": (lambda t: beam_ref.run_select(state, t=t), state["T"] - 1),
+    }
+    with torch.no_grad():
+        for name, (call, hi) in ops.items():
+            call(hi - 1)  # the last step of the range is taken
+            for t in (-1, hi):
+                with pytest.raises(ValueError, match=f"{name}: step {t} outside"):
+                    call(t)
+
+
 def test_embedding_step_is_the_full_pass_row():
     from csa_amd.model import Embeddings
     torch.manual_seed(0)
