@@ -5,8 +5,9 @@
 //
 // Fused path (d_k = 64, every config; below): k_rel_logits (C2P = Q LK^T, P2CT = K LQ^T), k_rel_prep
 // (permuted uint16 relation/mask code planes), k_rel_fwd_f (c2c MFMA + the two logit gathers, online
-// softmax, PV; saves the gathered bias tile-major), k_rel_bwd_qf / k_rel_bwd_kf (query / key side
-// backward, the gather backward as LDS bin histograms, no g/P materialised), k_rel_lgrad (dlk, dlq).
+// softmax, PV; saves the gathered bias tile-major), the query / key side backward (the gather backward
+// as LDS bin histograms, no g/P materialised): k_rel_bwd_qf / k_rel_bwd_kf in bf16 mode, k_rel_bwd_kh /
+// k_rel_bwd_qg in fp32; k_rel_lgrad (dlk, dlq).
 // Generic path (d_k = 16 / 32 / 96, tests only):
 //   Forward:  k_bgemm   C2P  = Q LK^T   (B,H,N,Lp)   p2c/c2p relation logits, as the reference's
 //             k_bgemm   P2CT = K LQ^T   (B,H,M,Lp)   lq @ k^T / q @ lk^T (disentangled_attn.py:53-58)
@@ -900,11 +901,12 @@ __global__ __launch_bounds__(64, 2) void k_rel_fwd_f(const RelArgs p) {
   }
 }
 
-// Backward, query side: one wave per (b,h, 32 queries), S^T orientation. Recomputes P and dP = dO V^T,
+// bf16-mode backward, query side (fp32 runs k_rel_bwd_kh / k_rel_bwd_qg below; every contraction here is a
+// bf16 MFMA): one wave per (b,h, 32 queries), S^T orientation. Recomputes P and dP = dO V^T,
 // g = P (dP - delta) / sqrt(3 d) (0 where masked); dq = g K + G_c2p LK with G_c2p[x][r] = sum over y
 // with rel[x][y] = r of g[x][y] accumulated in LDS bins (the gather backward of disentangled_attn.py:58);
 // writes dq, the G_c2p rows (for dlk) and (row max, 1/row sum, delta) per query for the key side.
-template <int D, bool BF>
+template <int D>
 __global__ __launch_bounds__(64, 1) void k_rel_bwd_qf(const RelArgs p) {
   constexpr int DT = D / 32, NS = D / 2, IMG = 32 * D * 4;
   static_assert(D == 64, "fused CSE path is d_k = 64");
@@ -966,26 +968,11 @@ __global__ __launch_bounds__(64, 1) void k_rel_bwd_qf(const RelArgs p) {
     f32x16 sacc = zero16(), dpacc = zero16();
     const int kb = row_base64(c, h, SW_BOTH);
     const int vbb = IMG + row_base64(c, h, SW_ROW);
-    if constexpr (BF) {
 #pragma unroll
-      for (int j2 = 0; j2 < NS / 8; ++j2) {
-        sacc = mfma_bf(pack8(lds_f4(lds, kb ^ (32 * j2)), lds_f4(lds, kb ^ (32 * j2 + 16))), pack8(&q[8 * j2]), sacc);
-        dpacc = mfma_bf(pack8(lds_f4(lds, vbb ^ (32 * j2)), lds_f4(lds, vbb ^ (32 * j2 + 16))), pack8(&dO[8 * j2]),
-                        dpacc);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NS / 4; ++j) {
-        const f32x4 kv = lds_f4(lds, kb ^ (16 * j));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sacc = mfma(kv[e], q[4 * j + e], sacc);
-      }
-#pragma unroll
-      for (int j = 0; j < NS / 4; ++j) {
-        const f32x4 vv = lds_f4(lds, vbb ^ (16 * j));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dpacc = mfma(vv[e], dO[4 * j + e], dpacc);
-      }
+    for (int j2 = 0; j2 < NS / 8; ++j2) {
+      sacc = mfma_bf(pack8(lds_f4(lds, kb ^ (32 * j2)), lds_f4(lds, kb ^ (32 * j2 + 16))), pack8(&q[8 * j2]), sacc);
+      dpacc = mfma_bf(pack8(lds_f4(lds, vbb ^ (32 * j2)), lds_f4(lds, vbb ^ (32 * j2 + 16))), pack8(&dO[8 * j2]),
+                      dpacc);
     }
     float kT[DT][16];
 #pragma unroll
@@ -1010,18 +997,11 @@ __global__ __launch_bounds__(64, 1) void k_rel_bwd_qf(const RelArgs p) {
       const float P = inside ? __expf(s - rmax) * rinv : 0.f;
       gv[r] = (inside && !msk) ? P * (dpacc[r] - delta) * p.inv_scale : 0.f;
     }
-    if constexpr (BF) {
-      const bf16x8 g0 = pack8(&gv[0]), g1 = pack8(&gv[8]);
+    const bf16x8 g0 = pack8(&gv[0]), g1 = pack8(&gv[8]);
 #pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        dq[t] = mfma_bf(pack8(&kT[t][0]), g0, dq[t]);
-        dq[t] = mfma_bf(pack8(&kT[t][8]), g1, dq[t]);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[t][r], gv[r], dq[t]);
+    for (int t = 0; t < DT; ++t) {
+      dq[t] = mfma_bf(pack8(&kT[t][0]), g0, dq[t]);
+      dq[t] = mfma_bf(pack8(&kT[t][8]), g1, dq[t]);
     }
     bins_scatter(bins, p.LB, gv, col);
   }
@@ -1065,11 +1045,12 @@ __global__ __launch_bounds__(256) void k_rel_qstat(const RelArgs p) {
   }
 }
 
-// Backward, key side: one wave per (b,h, 32 keys), S orientation (queries = accumulator rows, keys =
-// lanes); Q and dO tile images (SW_BOTH) and the per-query (max, 1/sum, delta) by LDS-DMA. dv = P^T dO,
+// bf16-mode backward, key side (bf16 MFMAs, as k_rel_bwd_qf): one wave per (b,h, 32 keys), S orientation
+// (queries = accumulator rows, keys = lanes); Q and dO tile images (SW_BOTH) and the per-query
+// (max, 1/sum, delta) by LDS-DMA. dv = P^T dO,
 // dk = g^T q + G_p2cT LQ with G_p2cT[y][r] = sum over x with rel[y][x] = r of g[x][y] in LDS bins
 // (the gather backward of disentangled_attn.py:55); writes dk, dv and the G_p2cT rows (for dlq).
-template <int D, bool BF>
+template <int D>
 __global__ __launch_bounds__(64, 1) void k_rel_bwd_kf(const RelArgs p) {
   constexpr int DT = D / 32, NS = D / 2, IMG = 32 * D * 4;
   static_assert(D == 64, "fused CSE path is d_k = 64");
@@ -1102,7 +1083,6 @@ __global__ __launch_bounds__(64, 1) void k_rel_bwd_kf(const RelArgs p) {
   dma64(Xl, xr_, xpat, xld, 0);
   dma_tile_contig<4>(Sl, sr_, 0);
   dma_block16<4096>(Rl, rbr, kbi * 4096);
-  const int rcol = 2 * IMG + 512 + 4 * rb_off(0, tile_pos(c));  // + 128 row: this key's bias in row `row`
   f32x16 dv[DT], dk[DT];
 #pragma unroll
   for (int t = 0; t < DT; ++t) { dv[t] = zero16(); dk[t] = zero16(); }
@@ -1120,30 +1100,13 @@ __global__ __launch_bounds__(64, 1) void k_rel_bwd_kf(const RelArgs p) {
       gl[r] = lds_f1(lds, 2 * IMG + 512 + 4 * rb_off(x, tile_pos(c)));
       col[r] = code_of(cm, r) & 0xffu;  // rel[y][x]: the p2c gather's column
     }
-    (void)rcol;
     f32x16 sacc = zero16(), dpacc = zero16();
     const int qrb = row_base64(c, h, SW_BOTH);
-    if constexpr (BF) {
 #pragma unroll
-      for (int j2 = 0; j2 < NS / 8; ++j2) {
-        sacc = mfma_bf(pack8(lds_f4(lds, qrb ^ (32 * j2)), lds_f4(lds, qrb ^ (32 * j2 + 16))), pack8(&kr[8 * j2]),
-                       sacc);
-        dpacc = mfma_bf(pack8(lds_f4(lds, IMG + (qrb ^ (32 * j2))), lds_f4(lds, IMG + (qrb ^ (32 * j2 + 16)))),
-                        pack8(&vr[8 * j2]), dpacc);
-      }
-    } else {
-#pragma unroll
-      for (int s4 = 0; s4 < NS / 4; ++s4) {
-        const f32x4 qv = lds_f4(lds, qrb ^ (16 * s4));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sacc = mfma(qv[e], kr[4 * s4 + e], sacc);
-      }
-#pragma unroll
-      for (int s4 = 0; s4 < NS / 4; ++s4) {
-        const f32x4 xv = lds_f4(lds, IMG + (qrb ^ (16 * s4)));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dpacc = mfma(xv[e], vr[4 * s4 + e], dpacc);
-      }
+    for (int j2 = 0; j2 < NS / 8; ++j2) {
+      sacc = mfma_bf(pack8(lds_f4(lds, qrb ^ (32 * j2)), lds_f4(lds, qrb ^ (32 * j2 + 16))), pack8(&kr[8 * j2]), sacc);
+      dpacc = mfma_bf(pack8(lds_f4(lds, IMG + (qrb ^ (32 * j2))), lds_f4(lds, IMG + (qrb ^ (32 * j2 + 16)))),
+                      pack8(&vr[8 * j2]), dpacc);
     }
     float Pv[16], gv[16];
 #pragma unroll
@@ -1160,27 +1123,16 @@ __global__ __launch_bounds__(64, 1) void k_rel_bwd_kf(const RelArgs p) {
     int cb[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t) cb[t] = both_base64(t, c, h);
-    if constexpr (BF) {
-      const bf16x8 p0 = pack8(&Pv[0]), p1 = pack8(&Pv[8]), g0 = pack8(&gv[0]), g1 = pack8(&gv[8]);
+    const bf16x8 p0 = pack8(&Pv[0]), p1 = pack8(&Pv[8]), g0 = pack8(&gv[0]), g1 = pack8(&gv[8]);
 #pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        float xc[16], qc[16];
+    for (int t = 0; t < DT; ++t) {
+      float xc[16], qc[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { xc[r] = both_read(lds, cb[t], r, IMG); qc[r] = both_read(lds, cb[t], r, 0); }
-        dv[t] = mfma_bf(pack8(&xc[0]), p0, dv[t]);
-        dv[t] = mfma_bf(pack8(&xc[8]), p1, dv[t]);
-        dk[t] = mfma_bf(pack8(&qc[0]), g0, dk[t]);
-        dk[t] = mfma_bf(pack8(&qc[8]), g1, dk[t]);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dv[t] = mfma(both_read(lds, cb[t], r, IMG), Pv[r], dv[t]);
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dk[t] = mfma(both_read(lds, cb[t], r, 0), gv[r], dk[t]);
+      for (int r = 0; r < 16; ++r) { xc[r] = both_read(lds, cb[t], r, IMG); qc[r] = both_read(lds, cb[t], r, 0); }
+      dv[t] = mfma_bf(pack8(&xc[0]), p0, dv[t]);
+      dv[t] = mfma_bf(pack8(&xc[8]), p1, dv[t]);
+      dk[t] = mfma_bf(pack8(&qc[0]), g0, dk[t]);
+      dk[t] = mfma_bf(pack8(&qc[8]), g1, dk[t]);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (qb + 1 < p.NQB) {
@@ -1779,11 +1731,6 @@ RelArgs make_rel(const csa_rel_attn_args* a, const RelLayout& R) {
 size_t bins_lds_bytes(const RelArgs& p) { return sizeof(float) * 32 * (size_t)p.LB; }
 size_t bins16_lds_bytes(const RelArgs& p) { return sizeof(float) * 2 * 16 * (size_t)p.LB16; }
 
-// fp32 backward on the 16-row kernels (two waves per SIMD); bf16 mode keeps the 32-row kernels.
-inline bool rel_use16(const RelArgs& p) {
-  return !p.bf16;
-}
-
 
 // relation logits: C2P[b,h] = Q LK_h^T (N x L), P2CT[b,h] = K LQ_h^T (N x L)
 void rel_logits(const csa_rel_attn_args* a, const RelLayout& R, hipStream_t st) {
@@ -1956,34 +1903,14 @@ csa_status csa_rel_attn_bwd(const csa_rel_attn_bwd_args* b, void* stream) {
   if (R.fused) {
     p.dk = b->dk; p.dv = b->dv; p.gc2p = gc2p; p.gp2ct = gp2ct;
     p.qstat = (float*)((char*)ws + R.qstat);
-    const bool w16 = rel_use16(p);
-    const size_t lq_bytes = w16 ? rel16_bins_off(false) + bins16_lds_bytes(p) : 2 * 32 * 64 * 4 + 4096 + bins_lds_bytes(p);
-    const size_t lk_bytes = w16 ? rel16_bins_off(true) + bins16_lds_bytes(p) : 2 * 32 * 64 * 4 + 512 + 4096 + bins_lds_bytes(p);
-    const dim3 gq(xcd_grid(p.NQB, B * H)), gk(xcd_grid(p.NKB, B * H)), blk(w16 ? 128 : 64);
-    const bool concur = b->side_stream && b->side_fork && b->side_join &&
-                        bwd_concurrent(b->schedule, b->side_stream, stream_device(st), (int64_t)p.NQB * B * H, 1);
-    const SideLane lane{(hipStream_t)b->side_stream, (hipEvent_t)b->side_fork, (hipEvent_t)b->side_join};
-    const SideLane* side = concur ? &lane : nullptr;
-    auto launch_q = [&](hipStream_t s_) {  // (bf16 mode: the fp32 path runs k_rel_bwd_qg below)
-      if (p.bf16) {
-        hipLaunchKernelGGL((k_rel_bwd_qf<64, true>), gq, blk, lq_bytes, s_, p);
-      } else {
-        hipLaunchKernelGGL((k_rel_bwd_qf<64, false>), gq, blk, lq_bytes, s_, p);
-      }
-    };
-    auto launch_k = [&](hipStream_t s_) {
-      if (w16) {
-        set_dyn_lds((const void*)k_rel_bwd_kh, (int)lk_bytes);
-        hipLaunchKernelGGL(k_rel_bwd_kh, gk, blk, lk_bytes, s_, p);
-      } else if (p.bf16) {
-        hipLaunchKernelGGL((k_rel_bwd_kf<64, true>), gk, blk, lk_bytes, s_, p);
-      } else {
-        hipLaunchKernelGGL((k_rel_bwd_kf<64, false>), gk, blk, lk_bytes, s_, p);
-      }
-    };
-    // fp32: row statistics, key side (g tiles out), then the query side from the key side's g tiles (no score / dP
-    // recompute on the query side; the round-3 recomputing query kernel measured slower, DESIGN.md §3 CSE A/B)
-    if (w16) {
+    const dim3 gq(xcd_grid(p.NQB, B * H)), gk(xcd_grid(p.NKB, B * H));
+    if (!p.bf16) {
+      // fp32, 16-row kernels (two waves per workgroup): row statistics, key side (g tiles out), then the query side
+      // from the key side's g tiles (no score / dP recompute on the query side; the round-3 recomputing query kernel
+      // measured slower, DESIGN.md §3 CSE A/B). In order on one stream: the query side reads what the key side wrote.
+      const dim3 blk(128);
+      const size_t lk_bytes = rel16_bins_off(true) + bins16_lds_bytes(p);
+      const size_t lg_bytes = rel16_bins_off(false) + bins16_lds_bytes(p);
       p.qstat_pre = 1;
       p.gt = (float*)((char*)ws + R.gt);
       const int64_t threads = 4LL * B * H * N;
@@ -1993,25 +1920,33 @@ csa_status csa_rel_attn_bwd(const csa_rel_attn_bwd_args* b, void* stream) {
       }
       {
         const RelStage sg(b->prof, CSA_REL_STAGE_BWD_K, st);
-        launch_k(st);
+        set_dyn_lds((const void*)k_rel_bwd_kh, (int)lk_bytes);
+        hipLaunchKernelGGL(k_rel_bwd_kh, gk, blk, lk_bytes, st, p);
       }
-      const size_t lg_bytes = rel16_bins_off(false) + bins16_lds_bytes(p);
       set_dyn_lds((const void*)k_rel_bwd_qg, (int)lg_bytes);
       const RelStage sg(b->prof, CSA_REL_STAGE_BWD_Q, st);
       hipLaunchKernelGGL(k_rel_bwd_qg, gq, blk, lg_bytes, st, p);
-    } else if (side) {  // fork: row statistics + key side on the side stream, query side here, join before the lgrad
-      if (!side->fork(st)) return rfail_hip("csa_rel_attn_bwd: side-stream fork");
-      p.qstat_pre = 1;
-      const int parts = w16 ? 4 : 2;
-      const int64_t threads = (int64_t)parts * B * H * N;
-      if (w16) hipLaunchKernelGGL(k_rel_qstat<4>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, side->s, p);
-      else hipLaunchKernelGGL(k_rel_qstat<2>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, side->s, p);
-      launch_k(side->s);
-      launch_q(st);
-      if (!side->join(st)) return rfail_hip("csa_rel_attn_bwd: side-stream join");
     } else {
-      launch_q(st);
-      launch_k(st);
+      // bf16 mode, 32-row kernels (one wave per workgroup): query side and key side are independent, in order or with
+      // the row statistics and the key side forked onto the side lane
+      const dim3 blk(64);
+      const size_t lq_bytes = 2 * 32 * 64 * 4 + 4096 + bins_lds_bytes(p);
+      const size_t lk_bytes = 2 * 32 * 64 * 4 + 512 + 4096 + bins_lds_bytes(p);
+      const bool concur = b->side_stream && b->side_fork && b->side_join &&
+                          bwd_concurrent(b->schedule, b->side_stream, stream_device(st), (int64_t)p.NQB * B * H, 1);
+      if (concur) {  // fork: row statistics + key side on the side stream, query side here, join before the lgrad
+        const SideLane side{(hipStream_t)b->side_stream, (hipEvent_t)b->side_fork, (hipEvent_t)b->side_join};
+        if (!side.fork(st)) return rfail_hip("csa_rel_attn_bwd: side-stream fork");
+        p.qstat_pre = 1;
+        const int64_t threads = 2LL * B * H * N;
+        hipLaunchKernelGGL(k_rel_qstat<2>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, side.s, p);
+        hipLaunchKernelGGL(k_rel_bwd_kf<64>, gk, blk, lk_bytes, side.s, p);
+        hipLaunchKernelGGL(k_rel_bwd_qf<64>, gq, blk, lq_bytes, st, p);
+        if (!side.join(st)) return rfail_hip("csa_rel_attn_bwd: side-stream join");
+      } else {
+        hipLaunchKernelGGL(k_rel_bwd_qf<64>, gq, blk, lq_bytes, st, p);
+        hipLaunchKernelGGL(k_rel_bwd_kf<64>, gk, blk, lk_bytes, st, p);
+      }
     }
     rel_param_grads(a, b, R, gc2p, gp2ct, st);
     return rcheck("csa_rel_attn_bwd");

@@ -204,6 +204,9 @@ __device__ __forceinline__ f32x4 frag4_lds(const float* __restrict__ f, int it, 
 // side(g) runs inside K-group g's scheduling region (g = 0 .. groups - 1; a compile-time constant once the loop is
 // unrolled): independent work (activation stores, ActStager) that the scheduler interleaves with the group's MFMAs.
 struct NoSide { __device__ __forceinline__ void operator()(int) const {} };
+// how many groups a chain has, i.e. for which g it calls side(g): S4N in fp32, S4N / 2 on the bf16 MFMA
+template <int S4N, bool BF16>
+constexpr int frag_chain_groups = BF16 ? S4N / 2 : S4N;
 template <int NTO, int S4N, int LA = 1, bool FL = false, bool BF16 = false, typename BV, typename SIDE = NoSide>
 __device__ __forceinline__ void frag_chain(const float* __restrict__ frag, int nsteps, f32x16 (&out)[NTO], BV bval,
                                            SIDE side = SIDE()) {
@@ -211,7 +214,7 @@ __device__ __forceinline__ void frag_chain(const float* __restrict__ frag, int n
   auto ld = [&](int t, int s4) { return FL ? frag4_lds(frag, t, nsteps, s4) : frag4(frag, t, nsteps, s4); };
   if constexpr (BF16) {
     static_assert(S4N % 2 == 0, "bf16 chains take K-groups in pairs");
-    constexpr int S8N = S4N / 2;
+    constexpr int S8N = frag_chain_groups<S4N, true>;
     f32x4 wq[2][NTO][2];
 #pragma unroll
     for (int t = 0; t < NTO; ++t) { wq[0][t][0] = ld(t, 0); wq[0][t][1] = ld(t, 1); }
@@ -389,7 +392,7 @@ struct KArgs {
   float *Qh, *Kh, *T, *stats, *Act;  // Act NULL for CSA_FLAG_FWD_ONLY (no activation blocks saved)
   uint32_t *Abits, *Rbits;
   uint32_t* cnt;  // per (b,h, query block) sampled-edge counts, summed per head by k_sparsity_finish
-  unsigned long long* tdead;  // per AST: fully masked key tiles (k_attn_fwd; bit 0 never set), NKB <= 64
+  unsigned long long* tdead;  // per AST: fully masked key tiles (k_attn_fwd; bit 0 never set), see TDEAD_TILES
   const float* U;
   uint32_t seed_lo, seed_hi, off;
   float attn_p, proj_p, scale;
@@ -422,7 +425,8 @@ __device__ __forceinline__ uint32_t u16_of(const u32x4& r, int e) {
 // mask keyed by (row, feature, layer, Q/K), so the backward regenerates it bit-identically.
 // The layer's Philox words (one call -> 8 x 16-bit uniforms for registers 8gp..8gp+7 of tile ot; keep <=>
 // u16 >= pdrop_thr) are generated one call per K-group as side work of the layer's own MFMA chain (gen(g) inside
-// the chain's scheduling regions), then applied (apply) to the finished accumulators. PD (a dropout launch): with
+// the chain's scheduling regions; u[g] is drawn only if the chain has a group g, which the static_asserts beside each
+// DropWords check against frag_chain_groups), then applied (apply) to the finished accumulators. PD (a dropout launch): with
 // p = 0 the keep test passes everywhere and the scale is 1, so PD only decides whether the words are drawn.
 template <int D, bool PD>
 struct DropWords {
@@ -460,8 +464,7 @@ struct DropWords {
 //   dC_h = sum dZ^T po = (sum dZ^T h2) W2^T + (sum dZ^T 1) b2^T     (po = h2 W2^T + b2, proj.6)
 // so the forward does not save po (a third of the activation bytes: 168 MB written and read per B = 256 step) and
 // k_cluster_grad applies W2 / b2 once per head. A reassociation of the same sums (fp32 rounding only).
-constexpr bool H2C_ON = true;
-__host__ __device__ constexpr bool h2c_path(int D, int KT, bool BF) { return H2C_ON && !BF && (D == 64 || D == 96) && KT == 1; }
+__host__ __device__ constexpr bool h2c_path(int D, int KT, bool BF) { return !BF && (D == 64 || D == 96) && KT == 1; }
 
 constexpr int MLP_LA = 2;  // forward MLP chains: fragments two K-groups ahead
 constexpr int FL_LA = 1;   // LDS fragment chains: one K-group ahead covers the LDS latency
@@ -495,6 +498,7 @@ __device__ __forceinline__ void mlp_layer0(const KArgs& p, const float* W0, cons
 #pragma unroll
   for (int ot = 0; ot < DT; ++ot) h1[ot] = zero16();
   DropWords<D, PD> dw(p, 0, row, bh, isK);
+  static_assert(frag_chain_groups<NS / 4, BF> >= DropWords<D, PD>::NC, "the chain must call gen(g) for every g < NC");
   frag_chain<DT, NS / 4, FL ? FL_LA : MLP_LA, FL, BF>(W0, NS, h1, [&](int s) { return x[s]; },
                                                        [&](int g) { dw.gen(g); });
   add_bias<D>(ba, h1);
@@ -852,6 +856,7 @@ __device__ __forceinline__ void proj_fwd_item(const KArgs& p, const FwdFrags& F,
   const __amdgpu_buffer_rsrc_t ars = make_rsrc(blk, on ? ABLK * 4 : 0);
   // layer 1's side work: h1's staged stores and layer 1's dropout words
   DropWords<D, PD> dw1(p, 1, row, bh, isK);
+  static_assert(frag_chain_groups<D / 8, BF> >= DropWords<D, PD>::NC, "layer 1's chain must call gen(g) for every g < NC");
   struct Side1 {
     ActStager<D / 32> st;
     DropWords<D, PD>* dw;
@@ -1003,9 +1008,11 @@ __global__ __launch_bounds__((64 * ProjFwdLds<D, KT>::NW)) void k_proj_fwd_l(con
   }
 }
 
+// The query side of the attention backward differs by dtype, and nothing else selects it.
 // fp32: k_attn_bwd_kv runs the elementwise backward once per element and hands the ds / G tiles to
 // k_attn_bwd_qg (which then recomputes neither S nor dP). bf16 mode: recomputing S and dP on the 16x faster bf16
-// MFMA costs less than moving the tiles through HBM, so k_attn_bwd_qr recomputes them (the round-3 design).
+// MFMA costs less than moving the tiles through HBM, so k_attn_bwd_qr recomputes them (the round-3 design) and
+// k_attn_bwd_kv stores no tiles.
 // Same-box A/B (profiles/r04_ab_handoff.txt): fp32 layer step 1.329 (recompute) -> 1.275 ms (handoff); saving the
 // forward's S tiles for k_attn_bwd_kv as well measured 1.290 ms (+23 us forward stores, -22 us backward): not kept.
 // One-plane handoff (no upstream map gradients): the key side stores w = dM P for an edge (A = 1) and the bit
@@ -1016,10 +1023,11 @@ __global__ __launch_bounds__((64 * ProjFwdLds<D, KT>::NW)) void k_proj_fwd_l(con
 // two-plane ds | G format, which the map-gradient variant (DG: per-element dgraph / dattn terms) keeps.
 constexpr uint32_t W_NO_EDGE = 0x7f800001u;
 
-template <bool BF>
-constexpr bool bwd_handoff() {
-  return !BF;
-}
+// The dead-tile record (KArgs::tdead): bit kt set = every key of 32-key tile kt is masked. k_attn_fwd writes it;
+// k_attn_bwd_kv and k_attn_bwd_qg skip the same tiles, so all three must agree on its reach (tdead_covers):
+// tile 0 is always live; more than 64 tiles: every tile live.
+constexpr int TDEAD_TILES = 64;
+__device__ __forceinline__ bool tdead_covers(int NKB) { return NKB <= TDEAD_TILES; }
 
 // ------------------------------------------------------------------------------------
 // F3: attention forward, one wave per (b, h, 32-query block), S^T orientation
@@ -1227,7 +1235,7 @@ __device__ __forceinline__ void attn_fwd_item(const KArgs& p, float* __restrict_
   // STE term reads them), no K / V images, no S or PV products. Tile 0, whose images the prologue loads, is always
   // processed as live. More than 64 key tiles: every tile live.
   uint64_t rem_live = 0, rem_dead = 0, dead = 0;
-  const bool tmask = p.NKB <= 64;
+  const bool tmask = tdead_covers(p.NKB);
   int kt = 0;
   // Philox words of tile kt (they depend only on (query, tile, head))
   auto philox_tile = [&](int kt_, u32x4 (&r_ste)[2], u32x4 (&r_drop)[2], bool with_drop = true) {
@@ -1730,10 +1738,10 @@ __device__ __forceinline__ void store_mb4(float* __restrict__ out, int nrows, in
 // B2 (bf16 mode): per (b,h, query block), S^T orientation: recompute S = QK^T and dP = dX V^T on bf16 MFMA,
 // the elementwise backward with the row constants of k_attn_rowprep (one record per lane: its query), then
 // dQ (attention path) = ds K, dQh = G T. The round-3 design, kept where recomputing is cheaper than the
-// k_attn_bwd_qg tile handoff (see bwd_handoff).
+// k_attn_bwd_qg tile handoff (see W_NO_EDGE). Every contraction is a bf16 MFMA.
 // ------------------------------------------------------------------------------------
 // DG: an upstream gradient of the graph and / or attn output is present (p.dgraph, p.dattn)
-template <int D, int KPH, bool DENSE, bool DROP, bool DG, bool BF>
+template <int D, int KPH, bool DENSE, bool DROP, bool DG>
 __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd_qr(const KArgs p) {
   using SH = AttnBwdShape<D, KPH>;
   constexpr int DT = D / 32, NS = D / 2, DP = SH::DP, KP = SH::KP, KPN = SH::KPN, KTA = SH::KTA;
@@ -1795,29 +1803,14 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
     f32x16 sacc = zero16(), dpacc = zero16();
     const int kb = SWZ ? row_base64(c, h, SW_BOTH) : 4 * (c * DP + NS * h);
     const int vb = SH::QV + (SWZ ? row_base64(c, h, SW_ROW) : 4 * (c * DP + NS * h));
-    if constexpr (BF) {
 #pragma unroll
-      for (int j2 = 0; j2 < NS / 8; ++j2) {
-        const f32x4 k0 = lds_f4(lds, SWZ ? (kb ^ (32 * j2)) : kb + 32 * j2);
-        const f32x4 k1 = lds_f4(lds, SWZ ? (kb ^ (32 * j2 + 16)) : kb + 32 * j2 + 16);
-        sacc = mfma_bf(pack8(k0, k1), pack8(&q[8 * j2]), sacc);
-        const f32x4 v0 = lds_f4(lds, SWZ ? (vb ^ (32 * j2)) : vb + 32 * j2);
-        const f32x4 v1 = lds_f4(lds, SWZ ? (vb ^ (32 * j2 + 16)) : vb + 32 * j2 + 16);
-        dpacc = mfma_bf(pack8(v0, v1), pack8(&dx[8 * j2]), dpacc);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NS / 4; ++j) {
-        const f32x4 kv = lds_f4(lds, SWZ ? (kb ^ (16 * j)) : kb + 16 * j);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sacc = mfma(kv[e], q[4 * j + e], sacc);
-      }
-#pragma unroll
-      for (int j = 0; j < NS / 4; ++j) {
-        const f32x4 vv = lds_f4(lds, SWZ ? (vb ^ (16 * j)) : vb + 16 * j);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dpacc = mfma(vv[e], dx[4 * j + e], dpacc);
-      }
+    for (int j2 = 0; j2 < NS / 8; ++j2) {
+      const f32x4 k0 = lds_f4(lds, SWZ ? (kb ^ (32 * j2)) : kb + 32 * j2);
+      const f32x4 k1 = lds_f4(lds, SWZ ? (kb ^ (32 * j2 + 16)) : kb + 32 * j2 + 16);
+      sacc = mfma_bf(pack8(k0, k1), pack8(&q[8 * j2]), sacc);
+      const f32x4 v0 = lds_f4(lds, SWZ ? (vb ^ (32 * j2)) : vb + 32 * j2);
+      const f32x4 v1 = lds_f4(lds, SWZ ? (vb ^ (32 * j2 + 16)) : vb + 32 * j2 + 16);
+      dpacc = mfma_bf(pack8(v0, v1), pack8(&dx[8 * j2]), dpacc);
     }
     // transposed operands of this tile's dQ / dQh products (lane d holds K[key crow(r,h)][d])
     float kT[DT][16], tT[KTA][16];
@@ -1872,18 +1865,11 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
       gv[r] = a ? __builtin_amdgcn_fmed3f(fmaf(dM, P, cg), -1.f, 1.f) : 0.f;  // STE.py:19 hardtanh(A * grad)
     }
     // dQ^T += K^T ds^T ; dQh^T += T^T G^T  (keys beyond M carry ds = G = 0)
-    if constexpr (BF) {
-      const bf16x8 s0 = pack8(&dsv[0]), s1 = pack8(&dsv[8]);
+    const bf16x8 s0 = pack8(&dsv[0]), s1 = pack8(&dsv[8]);
 #pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        dq[t] = mfma_bf(pack8(&kT[t][0]), s0, dq[t]);
-        dq[t] = mfma_bf(pack8(&kT[t][8]), s1, dq[t]);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[t][r], dsv[r], dq[t]);
+    for (int t = 0; t < DT; ++t) {
+      dq[t] = mfma_bf(pack8(&kT[t][0]), s0, dq[t]);
+      dq[t] = mfma_bf(pack8(&kT[t][8]), s1, dq[t]);
     }
     if constexpr (MB4) {
 #pragma unroll
@@ -1912,7 +1898,7 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
 // LDS per wave): the ds / G registers are refilled right behind the MFMAs that read them and the K / T
 // operands are read from LDS just before their MFMAs, and the other waves' MFMAs cover the load latency.
 // ------------------------------------------------------------------------------------
-template <int D, int KPH, bool DENSE, bool BF, bool W1>
+template <int D, int KPH, bool DENSE, bool W1>
 __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_qg(const KArgs p) {
   using SH = AttnBwdShape<D, KPH>;
   constexpr int DT = D / 32, DP = SH::DP, KP = SH::KP, KPN = SH::KPN, KTA = SH::KTA;
@@ -1968,7 +1954,7 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
   const float csp = (W1 && p.dsp) ? p.dsp[hd] / ((float)p.B * (float)p.N * (float)p.M) : 0.f;
   // key tiles whose every key is masked (the forward's record): their ds is 0 (P = 0), so no dQ products and no K
   // image; the T image and the tile (its A bits carry the STE term into dQh) still stream in
-  const uint64_t tdead = (p.mask && p.NKB <= 64) ? p.tdead[b] : 0ull;
+  const uint64_t tdead = (p.mask && tdead_covers(p.NKB)) ? p.tdead[b] : 0ull;
   CSA_ISSUE_BQ(0);
   load_tile(0);
   f32x16 dq[DT], dqh[KTA];
@@ -1977,7 +1963,9 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
 #pragma unroll
   for (int t = 0; t < KTA; ++t) dqh[t] = zero16();
   // the tile loop twice: without dead tiles (every unpadded batch: tdead is 0) the compiler folds the skips away and
-  // the body stays one scheduling region
+  // the body stays one scheduling region. The second copy must stay the first one's text. (Single-body forms tried:
+  // an always-inline lambda taking the record or 0 fails in the backend, "illegal VGPR to SGPR copy" on the DMA
+  // helpers' scalar operands; a two-pass unrolled outer loop compiles to different code in every instantiation.)
   if (tdead) {
     for (int kt = 0; kt < p.NKB; ++kt) {
       int ln = threadIdx.x;  // opaque per iteration: keeps the per-row LDS addresses out of the prologue
@@ -1987,14 +1975,14 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
       wait_vm_all();  // tile kt's K / T images and ds / G values (dead: bit words) have landed
       if constexpr (W1) {  // k_attn_bwd_kv's expressions (W_NO_EDGE)
         if ((tdead >> kt) & 1ull) {  // STE term only: G = A ? hardtanh(csp) : 0
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const bool a = (__float_as_uint(dsv[r]) >> c) & 1u;  // (the forward stores no bit for keys past M)
             gv[r] = a ? __builtin_amdgcn_fmed3f(0.f + csp, -1.f, 1.f) : 0.f;
             dsv[r] = 0.f;
           }
         } else {
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const bool a = __float_as_uint(dsv[r]) != W_NO_EDGE;
             const float w = a ? dsv[r] : 0.f;
@@ -2002,43 +1990,38 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
             dsv[r] = w;
           }
           if (rho != 0.f) {  // rare: a degenerate row (n < eps) also takes -rho P from the second plane
-  #pragma unroll
+#pragma unroll
             for (int r = 0; r < 16; ++r) dsv[r] = fmaf(-rho, tb[p.gplane + kt * 1024 + 32 * crow(r, h)], dsv[r]);
           }
         }
       }
       // dQ^T += K^T ds^T (lane d holds K[key crow(r,h)][d], read from the SW_COL / padded image per K-step)
-  #pragma unroll
+#pragma unroll
       for (int t = 0; t < (((tdead >> kt) & 1ull) ? 0 : DT); ++t) {
         const int cb = SH::GK + (SWZ ? col_base64(t, c, h) : 4 * (32 * t + c) + 16 * DP * h);
         float kT[16];
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) kT[r] = lds_f1(lds, cb + (SWZ ? 256 * crow(r, 0) : 4 * DP * crow(r, 0)));
-        if constexpr (BF) {
-          dq[t] = mfma_bf(pack8(&kT[0]), pack8(&dsv[0]), dq[t]);
-          dq[t] = mfma_bf(pack8(&kT[8]), pack8(&dsv[8]), dq[t]);
-        } else {
-  #pragma unroll
-          for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[r], dsv[r], dq[t]);
-        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[r], dsv[r], dq[t]);
       }
       // dQh^T += T^T G^T
       if constexpr (MB4) {  // lane (c, h): T[key crow(r,h)][cluster c & 15]
         float tT[16];
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) tT[r] = lds_f1(lds, SH::GT + narrow_elem(crow(r, h), c & 15, KPN));
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) dqh[0] = mfma4b(tT[r], gv[r], dqh[0]);
       } else if constexpr (!DENSE) {
-  #pragma unroll
+#pragma unroll
         for (int at = 0; at < KTA; ++at) {
           float tT[16];
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const float v = lds_f1(lds, SH::GT + narrow_elem(crow(r, h), imin(32 * at + c, KP - 1), KPN));
             tT[r] = (KP >= 32 || c < KP) ? v : 0.f;
           }
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) dqh[at] = mfma(tT[r], gv[r], dqh[at]);
         }
       }
@@ -2064,14 +2047,14 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
       wait_vm_all();  // tile kt's K / T images and ds / G values (dead: bit words) have landed
       if constexpr (W1) {  // k_attn_bwd_kv's expressions (W_NO_EDGE)
         if ((tdead >> kt) & 1ull) {  // STE term only: G = A ? hardtanh(csp) : 0
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const bool a = (__float_as_uint(dsv[r]) >> c) & 1u;  // (the forward stores no bit for keys past M)
             gv[r] = a ? __builtin_amdgcn_fmed3f(0.f + csp, -1.f, 1.f) : 0.f;
             dsv[r] = 0.f;
           }
         } else {
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const bool a = __float_as_uint(dsv[r]) != W_NO_EDGE;
             const float w = a ? dsv[r] : 0.f;
@@ -2079,43 +2062,38 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 8) ? 4 : 2) void k_attn_bwd_
             dsv[r] = w;
           }
           if (rho != 0.f) {  // rare: a degenerate row (n < eps) also takes -rho P from the second plane
-  #pragma unroll
+#pragma unroll
             for (int r = 0; r < 16; ++r) dsv[r] = fmaf(-rho, tb[p.gplane + kt * 1024 + 32 * crow(r, h)], dsv[r]);
           }
         }
       }
       // dQ^T += K^T ds^T (lane d holds K[key crow(r,h)][d], read from the SW_COL / padded image per K-step)
-  #pragma unroll
+#pragma unroll
       for (int t = 0; t < (((tdead >> kt) & 1ull) ? 0 : DT); ++t) {
         const int cb = SH::GK + (SWZ ? col_base64(t, c, h) : 4 * (32 * t + c) + 16 * DP * h);
         float kT[16];
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) kT[r] = lds_f1(lds, cb + (SWZ ? 256 * crow(r, 0) : 4 * DP * crow(r, 0)));
-        if constexpr (BF) {
-          dq[t] = mfma_bf(pack8(&kT[0]), pack8(&dsv[0]), dq[t]);
-          dq[t] = mfma_bf(pack8(&kT[8]), pack8(&dsv[8]), dq[t]);
-        } else {
-  #pragma unroll
-          for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[r], dsv[r], dq[t]);
-        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq[t] = mfma(kT[r], dsv[r], dq[t]);
       }
       // dQh^T += T^T G^T
       if constexpr (MB4) {  // lane (c, h): T[key crow(r,h)][cluster c & 15]
         float tT[16];
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) tT[r] = lds_f1(lds, SH::GT + narrow_elem(crow(r, h), c & 15, KPN));
-  #pragma unroll
+#pragma unroll
         for (int r = 0; r < 16; ++r) dqh[0] = mfma4b(tT[r], gv[r], dqh[0]);
       } else if constexpr (!DENSE) {
-  #pragma unroll
+#pragma unroll
         for (int at = 0; at < KTA; ++at) {
           float tT[16];
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) {
             const float v = lds_f1(lds, SH::GT + narrow_elem(crow(r, h), imin(32 * at + c, KP - 1), KPN));
             tT[r] = (KP >= 32 || c < KP) ? v : 0.f;
           }
-  #pragma unroll
+#pragma unroll
           for (int r = 0; r < 16; ++r) dqh[at] = mfma(tT[r], gv[r], dqh[at]);
         }
       }
@@ -2162,8 +2140,8 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
   constexpr int DT = D / 32, NS = D / 2, DP = SH::DP, KP = SH::KP, KPN = SH::KPN, KTA = SH::KTA;
   constexpr bool SWZ = SH::SWZ;
   constexpr bool MB4 = !DENSE && KP == 16;  // dT on mfma4b (store_mb4)
-  constexpr bool HO = bwd_handoff<BF>();    // ds / G tiles out for k_attn_bwd_qg (else k_attn_bwd_qr recomputes)
-  constexpr bool W1 = HO && !DENSE && !DG;  // one-plane w tiles (W_NO_EDGE)
+  constexpr bool HANDOFF = !BF;  // fp32: ds / G tiles out for k_attn_bwd_qg (bf16 mode: k_attn_bwd_qr recomputes)
+  constexpr bool W1 = HANDOFF && !DENSE && !DG;  // one-plane w tiles (W_NO_EDGE)
   constexpr bool PAIR = SWZ && !BF;  // dK / dV rows as d = 2m + t (b64 operand reads, pair_read)
   // FG (every variant without map gradients): the row constants are formed here from the forward's row statistics
   // and gamma = rowsum(dX * X), computed per query block from the dX image and the lane's X row; the key block 0
@@ -2238,7 +2216,9 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
   // tile is stored: those stores, a partial line per lane, cost more than the full loop, profiles/r06_dead_kv.txt).
   // Key block 0 always runs the full loop (with FG it forms the row constants the query side reads).
   bool dead = false;
-  if (mk && kbi > 0 && p.NKB <= 64) {  // (the forward's dead-tile record, which k_attn_bwd_qg reads, spans 64 tiles)
+  // (only tiles the forward's record, which k_attn_bwd_qg reads, can name; tdead_covers() written out: as a call it
+  // commutes the operands of one scalar AND in this kernel's code)
+  if (mk && kbi > 0 && p.NKB <= TDEAD_TILES) {
     wait_vm_all();
     dead = __builtin_amdgcn_ballot_w64(jv && mval == 0.f) == 0;
   }
@@ -2287,7 +2267,7 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
           }
           // one-plane format (W1): no w tile at all, k_attn_bwd_qg reads the tile's bits from the forward's words
           // (its tdead record); two planes: ds = 0 and G
-          if constexpr (HO && !W1) {
+          if constexpr (HANDOFF && !W1) {
             float* const w = dsw + (int64_t)qb * p.NKB * 1024 + 16 * half;
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
             {
@@ -2445,7 +2425,7 @@ __global__ __launch_bounds__(64, (D <= 64 && KPH <= 16) ? 2 : 1) void k_attn_bwd
             *reinterpret_cast<f32x4*>(wst + 2 * (rr & 4)) = f32x4{wv[0], wv[1], wv[2], wv[3]};
         }
       }
-      if constexpr (HO) {  // queries 16 half + 4 h + (0..3) and + 8: two f32x4 per tile, for ds and for G
+      if constexpr (HANDOFF) {  // queries 16 half + 4 h + (0..3) and + 8: two f32x4 per tile, for ds and for G
         float* const w = wst;
         // Plain (write-back) stores: a lane writes 16 B of its key's 128-B tile row per instruction, so a row is
         // completed by four instructions; non-temporal stores sent each 32-B piece on its own (round 6, same box:
@@ -3147,19 +3127,13 @@ __global__ __launch_bounds__(256, ProjBwdSmallShape<D>::LCS ? 1 : 2) void k_proj
   // orientation (lane = row) and as the 16x16x4 A operand (lane (c16, g4), step s: dT[row 4s + g4][c16]).
   // the item's hat block: its rows of Qh / Kh as k_proj_fwd_l stored them for the attention kernels ([row][16],
   // rows past the item's last row not fetched), so the forward saves no second copy in the activation block
-  // (HAT_ACT: the activation block's feature-major copy, the round-4 form)
-  constexpr bool HQK = true;
   auto prefetch_hat = [&](const Item& it) {
-    if constexpr (HQK) {
-      const int bh = it.b * p.H + hd, row0 = it.rb * 32;
-      const float* src = it.isK ? p.Kh + ((int64_t)bh * p.M + row0) * p.kp : p.Qh + ((int64_t)bh * p.N + row0) * p.kp;
-      dma_block16<2048>(HATl, make_rsrc(src, imin(32, it.nrows - row0) * p.kp * 4), 0);
-    } else {
-      dma_block16<2048>(HATl, act_rsrc(it), 96 * D * 4);
-    }
+    const int bh = it.b * p.H + hd, row0 = it.rb * 32;
+    const float* src = it.isK ? p.Kh + ((int64_t)bh * p.M + row0) * p.kp : p.Qh + ((int64_t)bh * p.N + row0) * p.kp;
+    dma_block16<2048>(HATl, make_rsrc(src, imin(32, it.nrows - row0) * p.kp * 4), 0);
   };
   // element (row, cluster f < 16) of the wave's hat block
-  auto hat_at = [&](int row, int f) { return HQK ? HATw[row * 16 + f] : HATw[act_off(f, row)]; };
+  auto hat_at = [&](int row, int f) { return HATw[row * 16 + f]; };
   auto prefetch = [&](const Item& it) {
     const int bh = it.b * p.H + hd, row0 = it.rb * 32;
     const float* src = it.isK ? p.dT + ((int64_t)bh * p.M + row0) * p.kp : p.dQh + ((int64_t)bh * p.N + row0) * p.kp;
@@ -3176,11 +3150,10 @@ __global__ __launch_bounds__(256, ProjBwdSmallShape<D>::LCS ? 1 : 2) void k_proj
     wait_vm_all();
     __syncthreads();
   }
-  if constexpr (HQK) {  // rows past an item's last row are never fetched: they only ever hold finite data
+  // hat rows past an item's last row are never fetched: they only ever hold finite data
 #pragma unroll
-    for (int e = 0; e < Sh::HATF / 64; ++e) HATw[lane + 64 * e] = 0.f;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
+  for (int e = 0; e < Sh::HATF / 64; ++e) HATw[lane + 64 * e] = 0.f;
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   prefetch_hat(item_of(0));
   prefetch(item_of(0));
   if constexpr (LW) load_wf(2);
@@ -3226,8 +3199,8 @@ __global__ __launch_bounds__(256, ProjBwdSmallShape<D>::LCS ? 1 : 2) void k_proj
     // ---- hat (acc orientation, clusters >= 16 are zero) and dZ = (S^T dT | dQh) * hat (1 - hat)
     f32x16 hat;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) hat[r] = r < 8 ? hat_at(c, crow(r, h)) : 0.f;
-    if constexpr (HQK) {  // registers 0-3 / 4-7 are clusters 4h .. 4h+3 / 8+4h .. of row c: two b128 reads
+    for (int r = 8; r < 16; ++r) hat[r] = 0.f;  // clusters >= 16
+    {  // registers 0-3 / 4-7 are clusters 4h .. 4h+3 / 8+4h .. of row c: two b128 reads
       const f32x4 h0 = *reinterpret_cast<const f32x4*>(HATw + c * 16 + 4 * h);
       const f32x4 h1 = *reinterpret_cast<const f32x4*>(HATw + c * 16 + 8 + 4 * h);
 #pragma unroll
@@ -3832,7 +3805,7 @@ csa_status launch_fwd(const csa_sbm_fwd_args* a, const Layout& L, hipStream_t st
 }
 
 // the row constants, then k_attn_bwd_kv (the elementwise backward; ds / G tiles out), then k_attn_bwd_qg, in
-// stream order (bf16 mode: k_attn_bwd_qr recomputes the query side instead of reading tiles, bwd_handoff).
+// stream order (bf16 mode: k_attn_bwd_qr recomputes the query side instead of reading tiles, see W_NO_EDGE).
 // mid(): enqueued between the key half and the query half (the concurrent schedule forks the projection
 // backward's key-block items there).
 template <int D, int KPH, bool DENSE, bool DROP, bool DG, bool BF, typename MID>
@@ -3851,13 +3824,13 @@ void launch_attn_bwd_v(const KArgs& p, int BH, const Layout& L, const csa_prof* 
   }
   mid();
   Stage sg(pf, CSA_STAGE_ATTN_BWD_Q, st);
-  if constexpr (bwd_handoff<BF>()) {
-    hipLaunchKernelGGL((k_attn_bwd_qg<D, KPH, DENSE, BF, !DENSE && !DG>), dim3(xcd_grid((int)L.NQB, BH)), dim3(64), SH::G_BYTES,
+  if constexpr (!BF) {
+    hipLaunchKernelGGL((k_attn_bwd_qg<D, KPH, DENSE, !DENSE && !DG>), dim3(xcd_grid((int)L.NQB, BH)), dim3(64), SH::G_BYTES,
                        st, p);
   } else {
     const size_t r_lds = SH::r_bytes((int)L.Mpad);
-    if (r_lds > 64 * 1024) set_dyn_lds((const void*)k_attn_bwd_qr<D, KPH, DENSE, DROP, DG, BF>, (int)r_lds);
-    hipLaunchKernelGGL((k_attn_bwd_qr<D, KPH, DENSE, DROP, DG, BF>), dim3(xcd_grid((int)L.NQB, BH)), dim3(64), r_lds,
+    if (r_lds > 64 * 1024) set_dyn_lds((const void*)k_attn_bwd_qr<D, KPH, DENSE, DROP, DG>, (int)r_lds);
+    hipLaunchKernelGGL((k_attn_bwd_qr<D, KPH, DENSE, DROP, DG>), dim3(xcd_grid((int)L.NQB, BH)), dim3(64), r_lds,
                        st, p);
   }
 }
@@ -4071,9 +4044,9 @@ csa_status csa_sbm_bwd(const csa_sbm_bwd_args* b, void* stream) {
   if (a->flags & CSA_FLAG_FWD_ONLY) return fail(CSA_INVALID_ARG, "the forward ran with CSA_FLAG_FWD_ONLY: no backward state");
   if ((a->flags & CSA_FLAG_BF16_WS) && a->dtype != CSA_DTYPE_BF16)
     return fail(CSA_INVALID_ARG, "CSA_FLAG_BF16_WS sizes the workspace of a CSA_DTYPE_BF16 call only");
-  // bf16 mode recomputes on the query side (bwd_handoff<true>() == false): no handoff tiles in its workspace
+  // bf16 mode recomputes on the query side (k_attn_bwd_qr): no handoff tiles in its workspace
   const Layout L = make_layout(a->B, a->H, a->N, a->M, a->d, a->k,
-                               a->flags | ((a->dtype == CSA_DTYPE_BF16 && !bwd_handoff<true>()) ? CSA_FLAG_BF16_WS : 0u));
+                               a->flags | (a->dtype == CSA_DTYPE_BF16 ? CSA_FLAG_BF16_WS : 0u));
   hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   if (a->d == 64) {
