@@ -28,6 +28,8 @@
  *   - fp32 data; device pointers; sizes and strides are int64 ELEMENT counts; the last
  *     (feature) dimension is always contiguous, so a (B,H,N,d) operand is described by its
  *     b/h/n strides (the non-contiguous split_heads view of sbm_attn.py:137-140 is accepted).
+ *   - The SBM and dense entry points (csa_sbm_fwd / csa_sbm_bwd / csa_sbm_maps) take N queries against
+ *     M keys and support N != M; the CSE relation attention (csa_rel_attn_*) is square by definition.
  *   - The caller allocates every output, the saved state and the workspace (sizes from the
  *     *_bytes() queries), and owns every stream and event: the library never allocates, never
  *     creates a stream or event, never synchronises the host and never throws. It enqueues

@@ -80,48 +80,54 @@ def tol_class(name):
 # cases: everything the oracle needs (kw: keyword arguments of closed_form.sbm_fwd_bwd / dense_fwd_bwd) and
 # everything the GPU run needs. Built on the CPU only (the budget test and the budget table use them too).
 # ---------------------------------------------------------------------------------------------------------
-def _attn_keep_mult(B, H, N, seed, offset, attn_p):
-    keep = philox.attn_keep(B, H, N, N, seed, offset, attn_p)
+def _attn_keep_mult(B, H, N, seed, offset, attn_p, M=None):
+    keep = philox.attn_keep(B, H, N, N if M is None else M, seed, offset, attn_p)
     return keep, torch.from_numpy(keep / (1.0 - np.float32(attn_p)))
 
 
-def sbm_case(shape, seed, train=False, mask=None, proj_p=0.1, maps=False):
+def sbm_case(shape, seed, train=False, mask=None, proj_p=0.1, maps=False, M=None):
+    """shape = (B, H, N, d, k); M keys (M = N when absent)."""
     B, H, N, d, k = shape
-    Q, K, V, rmask, u, dX, dsp, params = _rand_case(B, H, N, d, k, seed=seed)
+    M = N if M is None else M
+    Q, K, V, rmask, u, dX, dsp, params = _rand_case(B, H, N, d, k, seed=seed, M=M)
     mask = rmask if mask is None else mask
     kw = dict(Q=Q, K=K, V=V, mask=mask, params=params, u=u, num_clusters=k, dX=dX, dsparsity=dsp)
     c = dict(shape=shape, train=train, proj_p=proj_p if train else 0.0, attn_p=ATTN_P if train else 0.0, kw=kw)
     if train:
-        c["keep"], kw["attn_keep"] = _attn_keep_mult(B, H, N, SEED, OFFSET, ATTN_P)
+        c["keep"], kw["attn_keep"] = _attn_keep_mult(B, H, N, SEED, OFFSET, ATTN_P, M)
         kw["attn_p"] = ATTN_P
         if proj_p > 0:
             ks = 1.0 / (1.0 - np.float32(proj_p))
-            kw["proj_keep"] = {f"{s}{l}": torch.from_numpy(philox.proj_keep(B, H, N, d, SEED, OFFSET, proj_p, l,
-                                                                            int(s == "k")) * ks)
+            kw["proj_keep"] = {f"{s}{l}": torch.from_numpy(philox.proj_keep(B, H, M if s == "k" else N, d, SEED, OFFSET,
+                                                                            proj_p, l, int(s == "k")) * ks)
                                for s in "qk" for l in (0, 1)}
-        c["u16"] = philox.attn_uniforms(B, H, N, N, SEED, OFFSET, philox.RNG_STE)
+        c["u16"] = philox.attn_uniforms(B, H, N, M, SEED, OFFSET, philox.RNG_STE)
         kw["u"] = torch.from_numpy((c["u16"].astype(np.float64) + 0.5) / 65536.0)  # the oracle's own sampling
     if maps:
         g = torch.Generator().manual_seed(seed + 1)
-        kw["dgraph"] = 1e-3 * torch.randn(B, H, N, N, generator=g)
-        kw["dattn"] = torch.randn(B, H, N, N, generator=g)
+        kw["dgraph"] = 1e-3 * torch.randn(B, H, N, M, generator=g)
+        kw["dattn"] = torch.randn(B, H, N, M, generator=g)
     return c
 
 
-def dense_case(shape, seed, train=False, mask=None, with_dattn=False):
+def dense_case(shape, seed, train=False, mask=None, with_dattn=False, M=None):
+    """shape = (B, H, N, d); M keys (M = N when absent)."""
     B, H, N, d = shape
+    M = N if M is None else M
     g = torch.Generator().manual_seed(seed)
-    Q, K, V, dX = (torch.randn(B, H, N, d, generator=g) for _ in range(4))
+    Q = torch.randn(B, H, N, d, generator=g)
+    K, V = (torch.randn(B, H, M, d, generator=g) for _ in range(2))
+    dX = torch.randn(B, H, N, d, generator=g)
     if mask is None:
-        mask = torch.zeros(B, N)
-        mask[B - 1, N - N // 4:] = 1.0
+        mask = torch.zeros(B, M)
+        mask[B - 1, M - M // 4:] = 1.0
     kw = dict(Q=Q, K=K, V=V, mask=mask, dX=dX)
     c = dict(shape=shape, train=train, attn_p=ATTN_P if train else 0.0, kw=kw)
     if train:
-        c["keep"], kw["attn_keep"] = _attn_keep_mult(B, H, N, SEED, OFFSET, ATTN_P)
+        c["keep"], kw["attn_keep"] = _attn_keep_mult(B, H, N, SEED, OFFSET, ATTN_P, M)
         kw["attn_p"] = ATTN_P
     if with_dattn:
-        kw["dattn"] = torch.randn(B, H, N, N, generator=g)
+        kw["dattn"] = torch.randn(B, H, N, M, generator=g)
     return c
 
 
@@ -306,8 +312,7 @@ def check_sbm(c, got, label):
     """Graph, sparsity, X, dQ / dK / dV and every parameter gradient against closed_form(bf16=True) on the GPU's
     graph, under the ReLU-tie rule. Rows of an AST without a valid key are 0/0 in the reference: left out."""
     kw = c["kw"]
-    B, H, N, d, k = c["shape"]
-    live = kw["mask"].sum(1) < N
+    live = kw["mask"].sum(1) < kw["mask"].shape[1]
 
     def run_oracle(ov):
         return closed_form.sbm_fwd_bwd(**kw, graph_override=got["graph"], bf16=True, relu_override=ov)
@@ -329,8 +334,7 @@ def check_sbm(c, got, label):
 
 def check_dense(c, got, bf16, label):
     kw = c["kw"]
-    N = c["shape"][2]
-    live = kw["mask"].sum(1) < N
+    live = kw["mask"].sum(1) < kw["mask"].shape[1]
     ref, rg = closed_form.dense_fwd_bwd(**kw, bf16=bf16)
     if c["train"]:
         assert 0.75 < c["keep"].mean() < 0.85

@@ -251,15 +251,18 @@ def test_attention_layer_matches_reference(golden, case):
 
 
 
-def _rand_case(B, H, N, d, k, seed, pad=True):
+def _rand_case(B, H, N, d, k, seed, pad=True, M=None):
+    """N queries, M keys (M = N when absent: the same generator calls in the same order as ever)."""
+    M = N if M is None else M
     g = torch.Generator().manual_seed(seed)
-    Q, K, V = (torch.randn(B, H, N, d, generator=g) for _ in range(3))
-    mask = torch.zeros(B, N)
+    Q = torch.randn(B, H, N, d, generator=g)
+    K, V = (torch.randn(B, H, M, d, generator=g) for _ in range(2))
+    mask = torch.zeros(B, M)
     if pad:
         for b in range(B):
-            n = int(torch.randint(max(1, N // 3), N + 1, (1,), generator=g))
+            n = int(torch.randint(max(1, M // 3), M + 1, (1,), generator=g))
             mask[b, n:] = 1.0
-    u = torch.rand(B, H, N, N, generator=g)
+    u = torch.rand(B, H, N, M, generator=g)
     dX = torch.randn(B, H, N, d, generator=g)
     dsp = torch.full((H,), 3.125e-4)
     params = {"layer.weight": torch.nn.init.orthogonal_(torch.empty(H * k, d), generator=g)}
