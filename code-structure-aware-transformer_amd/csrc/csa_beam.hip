@@ -87,9 +87,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_row_topk(const float* __r
     }
   };
 
-  if ((V % 4 == 0) && (((uintptr_t)z) & 15) == 0) {
+  if (V % 4 == 0) {
+    // a base that is only 4-byte aligned loads the same four columns one by one: the thread's columns and the order of
+    // its sum do not depend on where the logits lie, so neither do the bits of lse
+    const bool vec = (((uintptr_t)z) & 15) == 0;
     for (int64_t c = 4 * (int64_t)tid; c < V; c += 4 * BEAM_THREADS) {
-      const f32x4 q = *reinterpret_cast<const f32x4*>(zr + c);
+      f32x4 q;
+      if (vec) q = *reinterpret_cast<const f32x4*>(zr + c);
+      else q = f32x4{zr[c], zr[c + 1], zr[c + 2], zr[c + 3]};
       const float mx = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[2], q[3]));
       if (mx > m) {
         s = (m > -INFINITY) ? s * expf(m - mx) : 0.f;

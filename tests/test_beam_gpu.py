@@ -104,8 +104,12 @@ def _ref_attention(q, k, v, mask, n):
     return torch.einsum("bhj,bhjd->bhd", s.softmax(-1), v).reshape(q.shape[0], -1)
 
 
+# (hd, keys); the last four: hd / 4 = 1, 3, 24 and 5 (3, 24 and 5 do not divide the wave), see test_decode_gpu.CASES
+ATTN_CASES = [(8, 1), (8, 7), (64, 64), (64, 65), (128, 130), (4, 70), (12, 65), (96, 150), (20, 130)]
+
+
 @pytest.mark.parametrize("W", [1, 3, 4])
-@pytest.mark.parametrize("hd,n", [(8, 1), (8, 7), (64, 64), (64, 65), (128, 130)])
+@pytest.mark.parametrize("hd,n", ATTN_CASES)
 def test_decode_attention_follows_the_ancestry_table(hd, n, W):
     """Self form: a random ancestry table inside each AST's W rows against the existing kernel on a cache gathered
     physically with torch (bitwise), and against fp64; only row (r, t) of the physical cache is written."""
@@ -141,7 +145,7 @@ def test_decode_attention_follows_the_ancestry_table(hd, n, W):
 
 
 @pytest.mark.parametrize("W", [1, 3, 4])
-@pytest.mark.parametrize("hd,n", [(8, 1), (8, 7), (64, 64), (64, 65), (128, 130)])
+@pytest.mark.parametrize("hd,n", ATTN_CASES)
 def test_decode_attention_shares_one_memory_per_group(hd, n, W):
     """Cross form: kv_group = W against the memory repeated W times (bitwise) and fp64, without a mask and with a
     mask whose row stride exceeds n."""

@@ -18,6 +18,10 @@ TINY = dict(src_vocab_size=50, tgt_vocab_size=60, hidden_size=64, num_heads=8, n
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs GPU")]
 
 CASES = [(2, 3, 8, 1), (2, 3, 8, 7), (1, 2, 64, 64), (1, 2, 64, 65), (2, 8, 64, 150), (1, 1, 128, 130), (1, 2, 32, 300)]
+# head dims whose float4 count hd / 4 does not divide the wave (64 % (hd / 4) lanes of the P.V phase idle), and hd = 4
+# (one key group per lane); test_row_kernels_gpu.py asserts that this list, STEP_CASES of test_decode_graph_gpu.py and
+# ATTN_CASES of test_beam_gpu.py keep them
+CASES += [(2, 3, 4, 70), (2, 3, 12, 65), (1, 5, 20, 130), (1, 2, 40, 64), (2, 2, 96, 150), (1, 3, 124, 67)]
 SENTINEL = 777.0
 
 

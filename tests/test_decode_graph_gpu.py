@@ -33,8 +33,13 @@ def _mask(kind, B, H, width, g):
     return m.cuda()
 
 
+# the last four: hd / 4 = 1, 3, 24 and 5 (3, 24 and 5 do not divide the wave), see test_decode_gpu.CASES
+STEP_CASES = [(3, 5, 8, 70), (2, 8, 64, 130), (1, 1, 128, 66), (3, 5, 4, 70), (2, 3, 12, 130), (1, 2, 96, 66),
+              (1, 5, 20, 130)]
+
+
 @pytest.mark.parametrize("mask_kind", ["batch", "per_head"])
-@pytest.mark.parametrize("B,H,hd,cap", [(3, 5, 8, 70), (2, 8, 64, 130), (1, 1, 128, 66)])
+@pytest.mark.parametrize("B,H,hd,cap", STEP_CASES)
 def test_device_step_attention_is_bitwise_the_host_step(B, H, hd, cap, mask_kind):
     """decode_attention with a tensor step equals the int-step call in `out` and in the whole cache, at both sides of
     the 64-key chunk boundary and at the last row; BH = 15 is not a multiple of the 4 waves of a workgroup. One counter

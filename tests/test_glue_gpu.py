@@ -20,9 +20,10 @@ def test_bias_grad_matches_column_sums(rows, cols):
 
 
 def test_bias_grad_back_to_back_on_two_streams():
-    """The one-launch path's per-stream arrival counters: many launches of different shapes queued back to
-    back (no synchronisation between them) on the default stream and on a side stream at once, each sum
-    checked. A counter not returned to 0 by its last workgroup would finish a later launch early."""
+    """Many calls of different shapes queued back to back (no synchronisation between them) on the default
+    stream and on a side stream at once, each sum checked. A call is two launches, the slice partials and
+    their sum, through a workspace of its own: a call that read another call's partials, or its own before
+    they were written, would show in its sum."""
     from csa_amd.glue import bias_grad
     shapes = [(9600, 512), (300, 2048), (9600, 64), (1, 40), (2500, 130), (16384, 96)] * 3
     g = torch.Generator().manual_seed(11)
