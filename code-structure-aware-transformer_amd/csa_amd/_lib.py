@@ -156,6 +156,21 @@ class BeamSelectArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class SampleRowsArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("logits", vp), ("rows", i64), ("V", i64), ("logits_stride", i64),
+        ("ys", vp), ("ys_stride", i64),
+        ("pad", vp), ("pad_stride", i64),
+        ("logp", vp), ("logp_stride", i64),
+        ("T", i64),
+        ("fin", vp),
+        ("inv_temperature", f32), ("top_p", f32),
+        ("top_k", i64),
+        ("eos_id", i64), ("pad_id", i64),
+        ("rng_dev", vp), ("t_dev", vp),
+    ]
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -255,6 +270,10 @@ def lib():
     L.csa_beam_select.argtypes = [ctypes.POINTER(BeamSelectArgs), vp]
     L.csa_decode_attn_beam.restype = ctypes.c_int
     L.csa_decode_attn_beam.argtypes = [ctypes.POINTER(DecodeAttnArgs), vp, vp, i64, i64, vp]
+    L.csa_sample_rows_supported.restype = ctypes.c_int  # v10 addition: sampled decoding
+    L.csa_sample_rows_supported.argtypes = [i64]
+    L.csa_sample_rows.restype = ctypes.c_int
+    L.csa_sample_rows.argtypes = [ctypes.POINTER(SampleRowsArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -285,4 +304,5 @@ EXPORTED_SYMBOLS = (
     "csa_decode_attn_supported", "csa_decode_attn", "csa_argmax_rows",
     "csa_decode_attn_step", "csa_decode_embed", "csa_argmax_rows_step",
     "csa_beam_supported", "csa_beam_row_topk", "csa_beam_select", "csa_decode_attn_beam",
+    "csa_sample_rows_supported", "csa_sample_rows",
 )

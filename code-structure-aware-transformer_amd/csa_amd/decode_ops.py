@@ -12,13 +12,17 @@ head dim run the same cached algorithm on F.scaled_dot_product_attention / torch
 Beam search (csrc/csa_beam.hip and the BEAM form of the attention kernel): decode_attention takes an ancestry table
 (anc=) or a row group sharing one memory (kv_group=), beam_row_topk gives each row's log-sum-exp and top-W logits and
 beam_select merges them per AST and rewrites the hypotheses' state in place. Each has the same kind of torch fallback,
-so the whole search also runs on the CPU."""
+so the whole search also runs on the CPU.
+
+Sampled decoding (csrc/csa_sample.hip): sample_rows filters each row of the logits by temperature, top-k and top-p,
+draws one token by Gumbel-max from a stateless Philox stream and writes it in place with its log-probability; its
+torch fallback restates the same rule, Philox included, in integer tensor ops."""
 import ctypes
 
 import torch
 import torch.nn.functional as F
 
-from ._lib import BeamSelectArgs, DecodeAttnArgs, check, lib, on_device
+from ._lib import BeamSelectArgs, DecodeAttnArgs, SampleRowsArgs, check, lib, on_device
 from .ops import _stream
 
 
@@ -393,3 +397,128 @@ def beam_select(topv, topi, lse, cum, fin, tokens, pad, anc, t, eos_id=None, pad
     else:
         _beam_select_ref(topv, topi, lse, cum, fin, tokens, pad, anc, _step_value(t, 0, T - 1, "beam_select"), eos,
                          int(pad_id), parent)
+
+
+# ---- sampled decoding: temperature, top-k, top-p and one Gumbel-max draw per row ----
+
+RNG_SAMPLE = 7  # Philox stream id of the sampling draws (counter word 3 high bits)
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo(a, x):
+    """(hi, lo) 32-bit words of the constant a times the 32-bit values held in the int64 tensor x, without leaving
+    int64: a * x is formed from the 16-bit halves of x."""
+    pl, ph = a * (x & 0xFFFF), a * (x >> 16)
+    low = pl + ((ph & 0xFFFF) << 16)
+    return (ph >> 16) + (low >> 32), low & _M32
+
+
+def _philox4x32(c0, c1, c2, c3, k0, k1, rounds=7):
+    """Philox4x32-7 (csrc/csa_common.hpp philox4x32) over int64 tensors holding 32-bit counter words."""
+    for _ in range(rounds):
+        h0, l0 = _mulhilo(0xD2511F53, c0)
+        h1, l1 = _mulhilo(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def _sample_gumbel(rows, V, t, seed, offset, device):
+    """g (rows, V) fp32: -log(-log u), u = ((w >> 9) + 0.5) 2^-23, w = word j & 3 of philox({j >> 2, r, t,
+    (RNG_SAMPLE << 28) ^ lo32(offset)}, seed)."""
+    j = torch.arange(V, dtype=torch.int64, device=device).view(1, V)
+    r = torch.arange(rows, dtype=torch.int64, device=device).view(rows, 1)
+    zero = torch.zeros(rows, V, dtype=torch.int64, device=device)
+    c3 = ((RNG_SAMPLE << 28) ^ (offset & _M32)) & _M32
+    words = _philox4x32((j >> 2) + zero, r + zero, zero + (t & _M32), zero + c3, seed & _M32, (seed >> 32) & _M32)
+    w = torch.stack(words, 0).gather(0, ((j & 3) + zero).unsqueeze(0))[0]
+    u = ((w >> 9).to(torch.float32) + 0.5) * (1.0 / 8388608.0)
+    return -torch.log(-torch.log(u))
+
+
+def _sample_rows_ref(z, ys, pad, fin, t, seed, offset, inv, top_k, top_p, eos, pad_id, logp):
+    """csa_sample_rows in plain torch: the same sets and the same fp32 noisy scores; the softmax masses of the top-p
+    rule and the log-sum-exp are summed in fp64."""
+    rows, V = z.shape
+    ninf = float("-inf")
+    y = z.float() * torch.tensor(inv, dtype=torch.float32, device=z.device)
+    keep = y > ninf  # neither -inf nor NaN
+    yc = torch.where(keep, y, torch.full_like(y, ninf))
+    ncand = keep.sum(1)
+    if top_k > 0:
+        srt = torch.sort(yc, dim=1, descending=True)[0]
+        theta = srt[:, min(top_k, V) - 1]
+        on = (ncand > top_k).unsqueeze(1)
+        keep = keep & (~on | (yc >= theta.unsqueeze(1)))
+    if top_p < 1.0:
+        y2 = torch.where(keep, yc, torch.full_like(yc, ninf)).double()
+        srt, order = torch.sort(y2, dim=1, descending=True)
+        p = torch.softmax(srt, dim=1)
+        p = torch.where(torch.isnan(p), torch.zeros_like(p), p)  # a row without candidates
+        before = torch.cumsum(p, 1) - p
+        start = torch.ones_like(srt, dtype=torch.bool)
+        start[:, 1:] = srt[:, 1:] != srt[:, :-1]
+        G = torch.cummax(torch.where(start, before, torch.full_like(before, -1.0)), dim=1)[0]  # the class's first entry
+        keep_sorted = G < float(torch.tensor(top_p, dtype=torch.float32))
+        keep = keep & torch.zeros_like(keep).scatter(1, order, keep_sorted)
+    score = torch.where(keep, y + _sample_gumbel(rows, V, t, seed, offset, z.device), torch.full_like(y, ninf))
+    tok = torch.argmax(score, dim=1)  # the first maximal entry
+    has = keep.any(1)
+    tok = torch.where(has, tok, torch.zeros_like(tok))
+    lse = torch.logsumexp(torch.where(keep, y, torch.full_like(y, ninf)).double(), dim=1)
+    lp = (y.gather(1, tok.unsqueeze(1))[:, 0].double() - lse).float()
+    lp = torch.where(has, lp, torch.full_like(lp, ninf))
+    done = fin != 0
+    tok = torch.where(done, torch.full_like(tok, pad_id), tok)
+    ys[:, t + 1] = tok
+    pad[:, t + 1] = tok == pad_id
+    if logp is not None:
+        logp[:, t] = torch.where(done, torch.zeros_like(lp), lp)
+    fin.copy_((done | (tok == eos)).to(torch.uint8))
+
+
+def sample_rows(z, ys, pad, fin, t_dev, rng, temperature=1.0, top_k=0, top_p=1.0, eos_id=None, pad_id=0, logp=None):
+    """One sampled token per row of the last-position logits z (rows, V), in place (csa_sample_rows, include/csa_hip.h).
+
+    y = fl32(z / temperature as a product with fl32(1) / fl32(temperature)); top_k > 0 keeps the entries at or above
+    the top_k-th largest value (all ties; off when it covers every candidate), top_p < 1 keeps, of the softmax over
+    that set, the classes of equal values whose strictly larger entries hold a mass below top_p; one Gumbel-max draw
+    over what is left (Philox stream 7, counter {j >> 2, row, t, offset}, key seed; lowest index on a tie). ys (rows, T)
+    int64, pad (rows, T) uint8 (row strides free, last dim contiguous), fin (rows,) uint8: ys[:, t+1] = token,
+    pad[:, t+1] = (token == pad_id), fin |= (token == eos_id) (None: never); a finished row takes pad_id. logp
+    (rows, T-1) fp32, optional, receives logp[:, t] = the token's log-probability under the filtered distribution
+    (0 for a finished row, -inf with token 0 for a row without a candidate). t_dev: the 1-element int32 step counter;
+    rng: a 2-element int64 tensor {seed, offset} on z's device, read on the device by the HIP kernel (a captured
+    graph draws anew once it is refilled). fp32 CUDA rows within csa_sample_rows_supported run the kernel, which
+    stores nothing for a step outside [0, T-1); anything else reads the counter and rng on the host."""
+    rows, V = z.shape
+    T = ys.shape[1] if ys.dim() == 2 else -1
+    dev = z.device
+    if (ys.dtype != torch.int64 or ys.dim() != 2 or ys.shape[0] != rows or ys.stride(1) != 1 or ys.device != dev
+            or pad.dtype != torch.uint8 or pad.shape != (rows, T) or pad.stride(1) != 1 or pad.device != dev
+            or fin.dtype != torch.uint8 or fin.shape != (rows,) or not fin.is_contiguous() or fin.device != dev
+            or (logp is not None and (logp.dtype != torch.float32 or logp.shape != (rows, T - 1) or logp.stride(1) != 1
+                                      or logp.device != dev))):
+        raise ValueError("sample_rows: ys (rows, T) int64, pad (rows, T) uint8, logp (rows, T-1) fp32, each with a "
+                         "contiguous last dim, and fin (rows,) uint8 contiguous, all on z's device")
+    if rng.dtype != torch.int64 or rng.shape != (2,) or not rng.is_contiguous() or rng.device != dev:
+        raise ValueError("sample_rows: rng is a 2-element int64 tensor {seed, offset} on z's device")
+    _check_step(t_dev, dev, "sample_rows")
+    temperature, top_k, top_p = float(temperature), int(top_k), float(top_p)
+    if not temperature > 0.0 or top_k < 0 or not top_p > 0.0 or T < 2:
+        raise ValueError("sample_rows: temperature > 0, top_k >= 0 (0: off), top_p > 0 (>= 1: off) and T >= 2")
+    inv = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(temperature, dtype=torch.float32))
+    eos = -1 if eos_id is None else int(eos_id)
+    if _rows_hip_ok(z) and bool(lib().csa_sample_rows_supported(V)):
+        a = SampleRowsArgs(logits=_ptr(z), rows=rows, V=V, logits_stride=z.stride(0), ys=_ptr(ys), ys_stride=ys.stride(0),
+                           pad=_ptr(pad), pad_stride=pad.stride(0), logp=_ptr(logp),
+                           logp_stride=logp.stride(0) if logp is not None else 0, T=T, fin=_ptr(fin),
+                           inv_temperature=inv, top_p=min(top_p, 1.0), top_k=min(top_k, 0x7fffffff), eos_id=eos,
+                           pad_id=int(pad_id), rng_dev=_ptr(rng), t_dev=_ptr(t_dev))
+        with on_device(dev):
+            check(lib().csa_sample_rows(ctypes.byref(a), _stream(dev)), "csa_sample_rows")
+        return ys
+    t = _step_value(t_dev, 0, T - 1, "sample_rows")
+    seed, offset = (int(v) & 0xFFFFFFFFFFFFFFFF for v in rng.tolist())
+    _sample_rows_ref(z, ys, pad, fin, t, seed, offset, inv, top_k, top_p, eos, int(pad_id), logp)
+    return ys

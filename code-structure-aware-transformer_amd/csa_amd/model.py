@@ -279,19 +279,26 @@ class BaseDecoder(nn.Module):
             out, w = mod(out, memory, tgt_mask=tgt_mask, memory_key_padding_mask=memory_key_padding_mask)
         return (self.norm(out) if self.norm is not None else out), w
 
-    def empty_cache(self, B, max_len, device, dtype, repeat_heads=False, beam=None, S=None):
+    def empty_cache(self, B, max_len, device, dtype, repeat_heads=False, beam=None, S=None, group=None):
         """A zeroed DecodeCache for B memory rows and up to max_len target positions: the one place that spells the
         layout (see DecodeCache). repeat_heads: key-pad the heads as forward() does when given
         make_std_mask(...).repeat(num_heads, 1, 1), the reference's decode(); otherwise head h of sample b sees sample
         b's PAD columns (a (B*H, T, T) mask built by repeat_interleave). beam=W: the cache of a beam search of width W,
         R = B * W self-attention rows, pad rows and ancestry rows over the B memory rows and the (B, S) memory mask (not
         with repeat_heads). S: also static memory_kv / memory_mask buffers for S source keys, which load_memory fills
-        in place (a captured graph keeps reading them); without S the memory side is left to the caller."""
+        in place (a captured graph keeps reading them); without S the memory side is left to the caller.
+        group=G: a group without ancestry, R = B * G self-attention and pad rows that each keep their own cache row
+        (anc stays None) over the B memory rows, kv_group = G: the independent samples of SamplingGenerator (not with
+        beam or repeat_heads)."""
         attn = self.layers[0].self_attn
         H, hd = attn.num_heads, attn.embed_dim // attn.num_heads
         if beam is not None and (repeat_heads or beam < 1):
             raise ValueError("make_cache: beam is a positive width and does not go with repeat_heads")
+        if group is not None and (repeat_heads or beam is not None or group < 1):
+            raise ValueError("make_cache: group is a positive count and does not go with beam or repeat_heads")
         R = B if beam is None else B * beam
+        if group is not None:
+            R = B * group
         z = lambda *shape, dt=dtype: torch.zeros(*shape, dtype=dt, device=device)
         kv = [z(2, R, H, max_len, hd) for _ in self.layers]
         return DecodeCache(self_k=[c[0] for c in kv], self_v=[c[1] for c in kv],
@@ -300,7 +307,7 @@ class BaseDecoder(nn.Module):
                            pad=z(R, max_len, dt=torch.uint8),
                            head_pad=z(B, H, max_len, dt=torch.uint8) if repeat_heads else None,
                            anc=None if beam is None else z(R, max_len, dt=torch.int32),
-                           kv_group=1 if beam is None else beam)
+                           kv_group=group if group is not None else 1 if beam is None else beam)
 
     def load_memory(self, cache, memory, memory_key_padding_mask):
         """A new batch-first memory (B, S, E) into the static buffers of an empty_cache(..., S=S) cache: every layer's
@@ -312,10 +319,10 @@ class BaseDecoder(nn.Module):
         else:
             cache.memory_mask.copy_(memory_key_padding_mask)
 
-    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False, beam=None):
+    def make_cache(self, memory, memory_key_padding_mask, max_len, repeat_heads=False, beam=None, group=None):
         """empty_cache for a batch-first memory (B, S, E), holding the memory projections themselves (no copy) and the
         mask as uint8, or None without one."""
-        cache = self.empty_cache(memory.shape[0], max_len, memory.device, memory.dtype, repeat_heads, beam)
+        cache = self.empty_cache(memory.shape[0], max_len, memory.device, memory.dtype, repeat_heads, beam, group=group)
         cache.memory_kv = [mod.multihead_attn.project_memory(memory) for mod in self.layers]
         if memory_key_padding_mask is not None:
             cache.memory_mask = memory_key_padding_mask.to(torch.uint8).contiguous()
@@ -738,6 +745,133 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         from ._lib import lib
         if not lib().csa_beam_supported(self.beam_size, self.max_tgt_len) or enc.dtype != torch.float32:
             raise ValueError("BeamSearchGenerator: graph=True needs fp32 and max_tgt_len <= 256 (csa_beam_supported)")
+
+
+class SamplingGenerator(_SteppedDecoding, nn.Module):
+    """Sampled decoding over the KV-cached, device-stepped decode step: num_samples independent draws per AST from the
+    model's distribution, filtered by temperature, top_k (0: off) and top_p (>= 1: off), with the log-probability of
+    every drawn token (no counterpart in the reference, whose only strategy is GreedyGenerator).
+
+    Rows are R = B * num_samples, row r = b * num_samples + s. Each row keeps its own self-attention cache row (no
+    ancestry table); the rows of an AST share one memory projection and mask (DecodeCache kv_group, make_cache's
+    group=). The self-attention key mask is the row's own PAD columns, as in BeamSearchGenerator and for its reason:
+    the reference decode()'s `.repeat(num_heads, 1, 1)` would let a finished sample's padding mask keys of live ones.
+    Per step the eval-mode generator logits go through decode_ops.sample_rows (csrc/csa_sample.hip): y = z /
+    temperature, top-k with all ties, top-p on the renormalised top-k set (tie-inclusive), one Gumbel-max draw from
+    Philox stream 7 keyed by (seed, row, step, column), logp = y[token] - lse(y over the kept set). A row that has
+    emitted eos_id is finished (None: never): it takes PAD with logp 0 and still runs through the decoder, ignored.
+    All max_tgt_len - 1 steps run (no early stop, static shapes).
+
+    forward(data, seed=None, return_logp=False) / sample(enc, src_mask, seed, return_logp) return the ids
+    (B, max_tgt_len - 1), or (B, num_samples, max_tgt_len - 1) when num_samples > 1, PAD after EOS; with return_logp
+    also the per-token log-probabilities of the same shape, 0 after EOS, whose sum over the last dim is the sequence
+    log-probability under the sampled (filtered) distribution. seed: a 64-bit key; None draws one from torch's CPU
+    generator (reproducible under torch.manual_seed). The same seed repeats the same draws on any device path.
+
+    graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
+    (..., temperature, top_k, top_p, num_samples, eos_id, return_logp, ...) (_SteppedDecoding); the seed lives in a
+    16-byte device buffer filled outside the graph, so a replay draws anew. Bitwise the eager result. Inference only:
+    a model in training mode raises."""
+
+    def __init__(self, model, max_tgt_len, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, eos_id=EOS,
+                 multi_gpu=False, graph=False):
+        super().__init__()
+        if not float(temperature) > 0.0:
+            raise ValueError("SamplingGenerator: temperature must be positive")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError("SamplingGenerator: top_k must be a non-negative integer (0 turns it off)")
+        if not float(top_p) > 0.0:
+            raise ValueError("SamplingGenerator: top_p must be positive (1 or more turns it off)")
+        if int(num_samples) != num_samples or num_samples < 1:
+            raise ValueError("SamplingGenerator: num_samples must be a positive integer")
+        if max_tgt_len < 2:
+            raise ValueError("SamplingGenerator: max_tgt_len must be at least 2")
+        self.model = model.module if multi_gpu else model
+        self.max_tgt_len = max_tgt_len
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.num_samples = int(num_samples)
+        self.eos_id = eos_id
+        self.start_pos = BOS
+        self._init_stepped(graph, group=self.num_samples)
+
+    def forward(self, data, seed=None, return_logp=False):
+        m = self.model
+        self._check_eval()
+        with torch.no_grad():
+            m.process_data(data)
+            enc, _, _, _, _ = m.encode(data)
+            return self.sample(enc, data.src_mask, seed, return_logp)
+
+    def sample(self, enc, src_mask=None, seed=None, return_logp=False):
+        """The decoder side alone: enc (B, S, E) batch-first memory (any source, CPU included), src_mask (B, S) bool
+        key-padding mask or None."""
+        self._check_eval()
+        return_logp = bool(return_logp)
+        if seed is None:  # one 64-bit Philox key per call from torch's global CPU generator, as ops._draw_seed
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        key = torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed, 0], dtype=torch.int64)  # {seed, offset}
+        T = self.max_tgt_len
+        with torch.no_grad():
+            if self.graph and enc.is_cuda:
+                extras = (self.temperature, self.top_k, self.top_p, self.num_samples, self.eos_id, return_logp)
+                e = self._graph_entry(enc, src_mask, extras, return_logp=return_logp)
+                e.rng.copy_(key)  # outside the graph: the replays read it on the device
+                for _ in range(T - 1):
+                    e.graph.replay()
+            else:
+                cache = self.model.decoder.make_cache(enc, src_mask, T, group=self.num_samples)
+                e = self._state(cache, return_logp)
+                self._reset(e)
+                e.rng.copy_(key)
+                for _ in range(T - 1):
+                    self._device_step(e)
+            shape = (enc.size(0), T - 1) if self.num_samples == 1 else (enc.size(0), self.num_samples, T - 1)
+            ids = e.ys[:, 1:].reshape(shape).clone()
+            return (ids, e.logp.reshape(shape).clone()) if return_logp else ids
+
+    def _check_eval(self):
+        if self.model.training:
+            raise RuntimeError("SamplingGenerator: inference only (the model is in training mode)")
+
+    def _state(self, cache, return_logp):
+        """The per-row state beside the cache: tokens, finished flag, the step counter, the {seed, offset} key that the
+        kernel reads on the device and, when asked for, the per-token log-probabilities."""
+        R, T, dev = cache.pad.shape[0], self.max_tgt_len, cache.pad.device
+        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
+        return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), fin=z(R, dtype=torch.uint8),
+                               t_dev=z(1, dtype=torch.int32), rng=z(2, dtype=torch.int64),
+                               logp=z(R, T - 1, dtype=torch.float32) if return_logp else None)
+
+    def _reset(self, e):
+        """Step 0 of a new batch: BOS everywhere, no row finished. The self-attention cache needs no reset (rows above t
+        are never read)."""
+        e.ys.zero_()
+        e.ys[:, 0] = self.start_pos
+        e.cache.pad.zero_()
+        e.fin.zero_()
+        if e.logp is not None:
+            e.logp.zero_()
+        e.t_dev.zero_()
+
+    def _device_step(self, e):
+        """One sampling step with every step-dependent index read from e.t_dev (on the device where the kernels run):
+        the same launches for every t. Ends by advancing the counter, after its last reader."""
+        from .decode_ops import sample_rows
+        m = self.model
+        x = m.tgt_embedding.step(e.ys, e.t_dev)
+        dec = m.decoder.step(x, e.cache, e.t_dev)
+        logits = m.generator.linear(dec[:, 0])
+        sample_rows(logits, e.ys, e.cache.pad, e.fin, e.t_dev, e.rng, temperature=self.temperature, top_k=self.top_k,
+                    top_p=self.top_p, eos_id=self.eos_id, pad_id=PAD, logp=e.logp)
+        e.t_dev.add_(1)
+
+    def _check_capture(self, enc):
+        from ._lib import lib
+        V = self.model.generator.linear.weight.shape[0]
+        if not lib().csa_sample_rows_supported(V) or enc.dtype != torch.float32:
+            raise ValueError("SamplingGenerator: graph=True needs fp32 and a target vocabulary of at most 32768 "
+                             "(csa_sample_rows_supported)")
 
 
 class _GatherTargets(torch.autograd.Function):

@@ -377,6 +377,38 @@ csa_status csa_beam_select(const csa_beam_select_args* a, void* stream);
 csa_status csa_decode_attn_beam(const csa_decode_attn_args* a, const int32_t* t_dev, const int32_t* anc,
                                 int64_t anc_stride, int64_t kv_group, void* stream);
 
+/* ---- v10 additions: sampled decoding (temperature, top-k, top-p) over the device-stepped decode step ----
+ * One Gumbel-max draw per row of the (rows, V) fp32 last-position logits, 1 <= V <= 32768 (csa_sample_rows_supported),
+ * at the step t read from t_dev; a t outside [0, T - 1) makes the launch store nothing and read no row. Per row r:
+ *   y_j = fl32(logits[r, j] * inv_temperature); -inf and NaN entries are never candidates;
+ *   top_k (0 < top_k < candidates, else off): kept are the y_j >= the top_k-th largest value, every tie included;
+ *   top_p (< 1, else off): with p the softmax of y over the top-k set, kept are the j whose strictly larger entries
+ *     hold a mass below top_p (whole classes of equal values; the maximal class always);
+ *   token = argmax over the kept j of fl32(y_j + g_j), the lowest index on a tie, g_j = -log(-log u_j),
+ *     u_j = ((w_j >> 9) + 0.5) * 2^-23, w_j = word j & 3 of Philox4x32-7 with counter {j >> 2, r, t,
+ *     (7 << 28) ^ lo32(offset)} and key (lo32(seed), hi32(seed)); {seed, offset} are read from rng_dev on the device,
+ *     so a captured graph draws anew whenever the caller rewrites those 16 bytes;
+ *   logp = y_token - log sum exp(y over the kept set). A row without a candidate gives token 0 and logp -inf.
+ * A row with fin[r] != 0 takes (pad_id, logp 0) and stays finished; otherwise fin[r] |= (token == eos_id), eos_id < 0:
+ * never. Stores ys[r, t + 1] = token, pad[r, t + 1] = (token == pad_id), logp[r, t] (logp may be NULL) and fin[r].
+ * Deterministic (fixed reduction orders, no float atomics; results do not depend on the logits' alignment), no
+ * allocation, no sync. */
+typedef struct csa_sample_rows_args {
+  const float* logits; int64_t rows, V, logits_stride;  /* (rows, V), row stride >= V */
+  int64_t* ys; int64_t ys_stride;                       /* (rows, T) in / out, row strides >= T */
+  uint8_t* pad; int64_t pad_stride;                     /* (rows, T) in / out: the self-attention key mask */
+  float* logp; int64_t logp_stride;                     /* (rows, T - 1) out, or NULL; row stride >= T - 1 */
+  int64_t T;
+  uint8_t* fin;                                         /* (rows) in / out */
+  float inv_temperature, top_p;                         /* 1 / temperature > 0; top_p > 0 */
+  int64_t top_k;                                        /* >= 0 */
+  int64_t eos_id, pad_id;
+  const uint64_t* rng_dev;                              /* {seed, offset} on the device, 8-byte aligned */
+  const int32_t* t_dev;
+} csa_sample_rows_args;
+int csa_sample_rows_supported(int64_t V);
+csa_status csa_sample_rows(const csa_sample_rows_args* a, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);
