@@ -171,6 +171,18 @@ class SampleRowsArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class ConstrainRowsArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("logits", vp), ("rows", i64), ("V", i64), ("logits_stride", i64),
+        ("ys", vp), ("ys_stride", i64), ("T", i64),
+        ("fin", vp),
+        ("repetition_penalty", f32),
+        ("no_repeat_ngram", i64), ("min_length", i64), ("eos_id", i64),
+        ("suppress", vp), ("n_suppress", i64),
+        ("t", i64), ("t_dev", vp),
+    ]
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -274,6 +286,10 @@ def lib():
     L.csa_sample_rows_supported.argtypes = [i64]
     L.csa_sample_rows.restype = ctypes.c_int
     L.csa_sample_rows.argtypes = [ctypes.POINTER(SampleRowsArgs), vp]
+    L.csa_constrain_rows_supported.restype = ctypes.c_int  # v10 addition: decoding constraints
+    L.csa_constrain_rows_supported.argtypes = [i64]
+    L.csa_constrain_rows.restype = ctypes.c_int
+    L.csa_constrain_rows.argtypes = [ctypes.POINTER(ConstrainRowsArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -305,4 +321,5 @@ EXPORTED_SYMBOLS = (
     "csa_decode_attn_step", "csa_decode_embed", "csa_argmax_rows_step",
     "csa_beam_supported", "csa_beam_row_topk", "csa_beam_select", "csa_decode_attn_beam",
     "csa_sample_rows_supported", "csa_sample_rows",
+    "csa_constrain_rows_supported", "csa_constrain_rows",
 )

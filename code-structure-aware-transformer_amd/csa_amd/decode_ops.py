@@ -16,13 +16,17 @@ so the whole search also runs on the CPU.
 
 Sampled decoding (csrc/csa_sample.hip): sample_rows filters each row of the logits by temperature, top-k and top-p,
 draws one token by Gumbel-max from a stateless Philox stream and writes it in place with its log-probability; its
-torch fallback restates the same rule, Philox included, in integer tensor ops."""
+torch fallback restates the same rule, Philox included, in integer tensor ops.
+
+Decoding constraints (csrc/csa_constrain.hip): constrain_rows rewrites the logits in place in front of any of the three
+selections (repetition penalty, no-repeat n-gram, minimum length, suppressed ids); its torch fallback is bitwise the
+kernel."""
 import ctypes
 
 import torch
 import torch.nn.functional as F
 
-from ._lib import BeamSelectArgs, DecodeAttnArgs, SampleRowsArgs, check, lib, on_device
+from ._lib import BeamSelectArgs, ConstrainRowsArgs, DecodeAttnArgs, SampleRowsArgs, check, lib, on_device
 from .ops import _stream
 
 
@@ -522,3 +526,100 @@ def sample_rows(z, ys, pad, fin, t_dev, rng, temperature=1.0, top_k=0, top_p=1.0
     seed, offset = (int(v) & 0xFFFFFFFFFFFFFFFF for v in rng.tolist())
     _sample_rows_ref(z, ys, pad, fin, t, seed, offset, inv, top_k, top_p, eos, int(pad_id), logp)
     return ys
+
+
+# ---- decoding constraints: repetition penalty, no-repeat n-gram, minimum length and suppressed ids ----
+
+MAX_SUPPRESS = 256  # entries of the suppress list (csa_constrain_rows)
+
+
+def _constrain_rows_ref(z, ys, t, fin, theta, ngram, min_length, eos, suppress):
+    """csa_constrain_rows in plain torch, in place: the same sets, and the penalty as the same two fp32 operations (a
+    division and a product by the fp32 theta held in a tensor, so neither becomes a product by a reciprocal), which
+    makes it bitwise the kernel."""
+    rows, V = z.shape
+    dev = z.device
+    L = t + 1
+    live = torch.ones(rows, 1, dtype=torch.bool, device=dev) if fin is None else (fin == 0).view(rows, 1)
+    h = ys[:, :L]
+    inr = (h >= 0) & (h < V)
+
+    def marks(tok, on):  # (rows, V) bool: the in-range tokens of tok where on; the others go to a spare column
+        m = torch.zeros(rows, V + 1, dtype=torch.bool, device=dev)
+        m.scatter_(1, torch.where(on & (tok >= 0) & (tok < V), tok, torch.full_like(tok, V)), True)
+        return m[:, :V]
+
+    if theta != 1.0:
+        th = torch.tensor(theta, dtype=torch.float32, device=dev)
+        zf = z.float()
+        z.copy_(torch.where(marks(h, inr) & live, torch.where(zf > 0, zf / th, zf * th).to(z.dtype), z))
+    ban = torch.zeros(rows, V, dtype=torch.bool, device=dev)
+    if 1 <= ngram <= L:
+        match = torch.ones(rows, L - ngram + 1, dtype=torch.bool, device=dev)
+        for k in range(ngram - 1):  # h[i + k] == h[L - (n - 1) + k] for every start i at once
+            match &= h[:, k:k + L - ngram + 1] == h[:, L - ngram + 1 + k].unsqueeze(1)
+        ban |= marks(h[:, ngram - 1:], match)
+    if 0 <= eos < V and t < min_length:
+        ban[:, eos] = True
+    if suppress is not None and suppress.numel():
+        s = suppress.long().view(1, -1).expand(rows, -1)
+        ban |= marks(s, torch.ones_like(s, dtype=torch.bool))
+    z.masked_fill_(ban & live, float("-inf"))
+
+
+def constrain_rows(z, ys, t, *, fin=None, repetition_penalty=1.0, no_repeat_ngram=0, min_length=0, eos_id=None,
+                   suppress=None):
+    """Decoding constraints on the last-position logits z (rows, V), in place (csa_constrain_rows, include/csa_hip.h),
+    in front of argmax_rows / beam_row_topk / sample_rows, which see a banned token as a -inf logit.
+
+    ys (rows, T) int64 token buffer (row stride free, last dim contiguous); the history of row r at step t is
+    ys[r, 0..t], the literal columns. t: the 1-element int32 step counter or an int in [0, T-1). fin (rows,) uint8,
+    optional: a row with fin != 0 is left untouched. repetition_penalty theta > 0 (1: off): each distinct in-range
+    history token's logit becomes z / theta if z > 0 else z * theta, once. no_repeat_ngram n >= 0 (0: off): a token that
+    would complete an n-gram already in the history is banned. min_length: eos_id (None: off) is banned while
+    t < min_length. suppress: an int32 tensor of at most 256 ids on z's device, banned at every step (ids outside
+    [0, V) are ignored). A ban stores -inf and wins over the penalty. z: rows with a contiguous last dim and a row
+    stride >= V. fp32 CUDA rows with T within csa_constrain_rows_supported run the kernel, which stores nothing for a
+    counter outside [0, T-1); anything else reads the counter on the host and runs the same fp32 operations in torch,
+    bitwise the kernel. Returns z."""
+    if (z.dim() != 2 or not z.is_floating_point() or (z.shape[1] > 1 and z.stride(1) != 1)
+            or (z.shape[0] > 1 and z.stride(0) < z.shape[1])):
+        raise ValueError("constrain_rows: z must be (rows, V) floating point with a contiguous last dim and a row stride "
+                         "of at least V")
+    rows, V = z.shape
+    T = ys.shape[1] if ys.dim() == 2 else -1
+    dev = z.device
+    if (ys.dtype != torch.int64 or ys.dim() != 2 or ys.shape[0] != rows or ys.stride(1) != 1 or ys.device != dev
+            or (fin is not None and (fin.dtype != torch.uint8 or fin.shape != (rows,) or not fin.is_contiguous()
+                                     or fin.device != dev))):
+        raise ValueError("constrain_rows: ys (rows, T) int64 with a contiguous last dim and fin (rows,) uint8 contiguous, "
+                         "on z's device")
+    if suppress is not None and (not isinstance(suppress, torch.Tensor) or suppress.dtype != torch.int32
+                                 or suppress.dim() != 1 or suppress.numel() > MAX_SUPPRESS
+                                 or not suppress.is_contiguous() or suppress.device != dev):
+        raise ValueError("constrain_rows: suppress is a contiguous int32 tensor of at most 256 ids on z's device")
+    theta = float(torch.tensor(float(repetition_penalty), dtype=torch.float32))  # the fp32 value the kernel takes
+    if int(no_repeat_ngram) != no_repeat_ngram or int(min_length) != min_length:
+        raise ValueError("constrain_rows: no_repeat_ngram and min_length are integers")
+    ngram, min_length = int(no_repeat_ngram), int(min_length)
+    if not 0.0 < theta < float("inf") or ngram < 0 or min_length < 0 or T < 2:
+        raise ValueError("constrain_rows: repetition_penalty in (0, inf) (1: off), no_repeat_ngram >= 0 (0: off), "
+                         "min_length >= 0 and T >= 2")
+    eos = -1 if eos_id is None or int(eos_id) < 0 else int(eos_id)
+    step = _is_step(t)
+    if step:
+        _check_step(t, dev, "constrain_rows")
+    else:
+        t = _step_value(t, 0, T - 1, "constrain_rows")
+    if z.is_cuda and z.dtype == torch.float32 and bool(lib().csa_constrain_rows_supported(T)):
+        a = ConstrainRowsArgs(logits=_ptr(z), rows=rows, V=V, logits_stride=z.stride(0) if rows > 1 else max(z.stride(0), V),
+                              ys=_ptr(ys), ys_stride=ys.stride(0) if rows > 1 else max(ys.stride(0), T), T=T,
+                              fin=_ptr(fin), repetition_penalty=theta, no_repeat_ngram=ngram, min_length=min_length,
+                              eos_id=eos, suppress=_ptr(suppress) if suppress is not None and suppress.numel() else None,
+                              n_suppress=suppress.numel() if suppress is not None else 0,
+                              t=0 if step else t, t_dev=_ptr(t) if step else None)
+        with on_device(dev):
+            check(lib().csa_constrain_rows(ctypes.byref(a), _stream(dev)), "csa_constrain_rows")
+        return z
+    _constrain_rows_ref(z, ys, _step_value(t, 0, T - 1, "constrain_rows"), fin, theta, ngram, min_length, eos, suppress)
+    return z

@@ -17,7 +17,9 @@ reference's and reference checkpoints load. What changes:
 """
 import copy
 import math
+from dataclasses import dataclass
 from types import SimpleNamespace
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -465,12 +467,72 @@ class GreedyGenerator(nn.Module):
         return ys[:, 1:]
 
 
+@dataclass(frozen=True)
+class DecodingConstraints:
+    """Which tokens a decoding step may choose, for CachedGreedyGenerator, BeamSearchGenerator and SamplingGenerator
+    (decode_ops.constrain_rows, csrc/csa_constrain.hip): a frozen, hashable value.
+
+    repetition_penalty theta > 0 (1: off): the logit z of every token already in the row's history, BOS included,
+    becomes z / theta if z > 0 else z * theta, once however often the token occurs. no_repeat_ngram_size n >= 0 (0: off):
+    a token that would complete an n-gram the history already holds is banned. min_length: eos_id is banned at the
+    steps t < min_length, so an output holds at least min_length tokens before its EOS (off at 0 or with eos_id None).
+    suppress_ids: at most 256 ids banned at every step. A banned token is a -inf logit to the selection that follows,
+    which renormalises over what is left. `active` is False when every rule is off; the generators then run exactly
+    the launches they run without constraints."""
+
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_length: int = 0
+    suppress_ids: tuple = ()
+    eos_id: Optional[int] = EOS
+
+    MAX_SUPPRESS = 256
+
+    def __post_init__(self):
+        theta = float(self.repetition_penalty)
+        if not 0.0 < theta < float("inf"):
+            raise ValueError("DecodingConstraints: repetition_penalty must be positive and finite (1 turns it off)")
+        for name in ("no_repeat_ngram_size", "min_length"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError(f"DecodingConstraints: {name} must be a non-negative integer (0 turns it off)")
+        ids, eos = tuple(self.suppress_ids), self.eos_id
+        if len(ids) > self.MAX_SUPPRESS or any(isinstance(i, bool) or int(i) != i or not 0 <= i < 2 ** 31 for i in ids):
+            raise ValueError("DecodingConstraints: suppress_ids holds at most 256 non-negative integer ids")
+        if eos is not None and (isinstance(eos, bool) or int(eos) != eos or eos < 0):
+            raise ValueError("DecodingConstraints: eos_id must be a non-negative integer or None")
+        for name, v in (("repetition_penalty", theta), ("no_repeat_ngram_size", int(self.no_repeat_ngram_size)),
+                        ("min_length", int(self.min_length)), ("suppress_ids", tuple(int(i) for i in ids)),
+                        ("eos_id", None if eos is None else int(eos))):
+            object.__setattr__(self, name, v)  # the normalised value (frozen: no plain assignment)
+
+    @property
+    def active(self):
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or bool(self.suppress_ids)
+                or (self.min_length > 0 and self.eos_id is not None))
+
+    def apply(self, logits, ys, t, fin=None, suppress=None):
+        """One constrain_rows call with this value's rules; suppress: suppress_tensor(device) made once."""
+        from .decode_ops import constrain_rows
+        return constrain_rows(logits, ys, t, fin=fin, repetition_penalty=self.repetition_penalty,
+                              no_repeat_ngram=self.no_repeat_ngram_size, min_length=self.min_length, eos_id=self.eos_id,
+                              suppress=suppress)
+
+    def suppress_tensor(self, device):
+        """The suppress list as the static int32 device tensor that the kernel reads, or None for an empty list."""
+        return torch.tensor(self.suppress_ids, dtype=torch.int32, device=device) if self.suppress_ids else None
+
+
 class _SteppedDecoding:
     """graph=True of CachedGreedyGenerator and BeamSearchGenerator: the device-stepped decode step (every kernel reads
     the step from the 4-byte device counter e.t_dev, so every step issues the same launches), captured once per
     (device, B, S, max_tgt_len, the generator's key extras, parameter addresses) as one single-stream
     torch.cuda.CUDAGraph over static buffers and replayed max_tgt_len - 1 times per call. `captures` counts the graphs
-    captured. The generator supplies _state(cache, **kw), _reset(e), _device_step(e) and, if it must, _check_capture."""
+    captured. The generator supplies _state(cache, **kw), _reset(e), _device_step(e) and, if it must, _check_capture.
+
+    constraints= (a DecodingConstraints) is shared by the three generators: when active, one decode_ops.constrain_rows
+    call sits between generator.linear and the selection of every step, the value joins the graph key extras and the
+    suppress list is a static device tensor of the state; None or an inactive value changes nothing."""
 
     MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
 
@@ -481,6 +543,34 @@ class _SteppedDecoding:
         self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
         self._cache_options = cache_options  # what the generator asks of BaseDecoder.empty_cache
 
+    @property
+    def constraints(self):
+        """The active DecodingConstraints, or None. Assignable between calls: None and an inactive value are the same
+        thing, no constraint step at all (the launches, the graph key and the captured graph of a generator built
+        without the keyword); another active value gets a captured graph of its own."""
+        return self._constraints
+
+    @constraints.setter
+    def constraints(self, constraints):
+        if constraints is not None and not isinstance(constraints, DecodingConstraints):
+            raise TypeError("constraints must be a DecodingConstraints or None")
+        object.__setattr__(self, "_constraints", constraints if constraints is not None and constraints.active else None)
+
+    def _suppress_state(self, device):
+        """The suppress list as the static device tensor of a step's state (None without one)."""
+        return None if self.constraints is None else self.constraints.suppress_tensor(device)
+
+    def _constraint_key(self):
+        """What the constraints add to the graph key extras: nothing when there are none."""
+        return () if self.constraints is None else (self.constraints,)
+
+    def _check_constraints_capture(self, enc):
+        from ._lib import lib
+        if self.constraints is not None and (not lib().csa_constrain_rows_supported(self.max_tgt_len)
+                                             or enc.dtype != torch.float32):
+            raise ValueError(f"{type(self).__name__}: graph=True with constraints needs fp32 and max_tgt_len <= 1024 "
+                             "(csa_constrain_rows_supported)")
+
     def _step_params(self):
         m = self.model
         mods = (m.tgt_embedding, m.decoder, m.generator.linear)
@@ -488,6 +578,7 @@ class _SteppedDecoding:
 
     def _check_capture(self, enc):
         """Raises where the generator's step cannot be captured for this memory."""
+        self._check_constraints_capture(enc)
 
     def _capture(self, enc, **state_kw):
         self._check_capture(enc)
@@ -544,15 +635,24 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
     from Python. The step is instead run device-stepped (csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step)
     and replayed from one captured graph per (..., return_logp, ...) (_SteppedDecoding); process_data, encode (its
     Philox key comes from the CPU generator) and the memory projections stay eager. Same ids and log-probabilities,
-    bitwise."""
+    bitwise.
 
-    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False):
+    constraints=DecodingConstraints(...): the logits of every step go through decode_ops.constrain_rows before the
+    argmax (history = the row's tokens so far, BOS included; there is no finished flag here, so the rules keep applying
+    after an EOS), and return_logp reports the constrained distribution. Training mode with active constraints
+    raises: the uncached loop it defers to has no such step."""
+
+    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False, constraints=None):
         super().__init__(model, max_tgt_len, multi_gpu)
         self._init_stepped(graph, repeat_heads=True)  # as CSATrans.decode masks
+        self.constraints = constraints
 
     def forward(self, data, return_logp=False):
         m = self.model
         if m.training:
+            if self.constraints is not None:
+                raise RuntimeError("CachedGreedyGenerator: constraints are for inference only (the uncached loop that "
+                                   "training mode defers to has no constraint step)")
             ys = super().forward(data)
             return (ys, None) if return_logp else ys
         from .decode_ops import argmax_rows
@@ -567,10 +667,14 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
             ys = torch.zeros(B, T, dtype=torch.long, device=enc.device)
             ys[:, 0] = self.start_pos
             logps = []
+            con = self.constraints
+            suppress = None if con is None else con.suppress_tensor(enc.device)
             for t in range(T - 1):
                 x = m.tgt_embedding.step(ys[:, t:t + 1], t)
                 dec = m.decoder.step(x, cache, t)
                 logits = m.generator.linear(dec[:, 0])
+                if con is not None:
+                    con.apply(logits, ys, t, suppress=suppress)
                 argmax_rows(logits, out=ys[:, t + 1], is_pad=cache.pad[:, t + 1], pad_id=PAD)
                 if return_logp:
                     logps.append(gen_log_softmax(logits, 0.0))
@@ -585,7 +689,7 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
         B, T = cache.pad.shape
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=cache.pad.device)
         return SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None,
-                               return_logp=return_logp)
+                               return_logp=return_logp, suppress=self._suppress_state(cache.pad.device))
 
     def _device_step(self, e):
         """One decode step with every step-dependent index read from e.t_dev on the device: the same launches for
@@ -596,6 +700,8 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
         x = m.tgt_embedding.step(e.ys, e.t_dev)
         dec = m.decoder.step(x, e.cache, e.t_dev)
         logits = m.generator.linear(dec[:, 0])
+        if self.constraints is not None:
+            self.constraints.apply(logits, e.ys, e.t_dev, suppress=e.suppress)
         argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
         e.logp = gen_log_softmax(logits, 0.0) if e.return_logp else None
         e.t_dev.add_(1)
@@ -610,7 +716,7 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
 
     def _forward_graph(self, data, enc, return_logp):
         return_logp = bool(return_logp)
-        e = self._graph_entry(enc, data.src_mask, (return_logp,), return_logp=return_logp)
+        e = self._graph_entry(enc, data.src_mask, (return_logp, *self._constraint_key()), return_logp=return_logp)
         logps = []
         for _ in range(self.max_tgt_len - 1):
             e.graph.replay()
@@ -644,9 +750,14 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
 
     graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
     (..., beam_size, ...) (_SteppedDecoding); bitwise the eager result. Inference only: a model in training mode
-    raises."""
+    raises.
 
-    def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False):
+    constraints=DecodingConstraints(...): every live hypothesis' logits go through decode_ops.constrain_rows (its own
+    history, as the selection rewrote it) before the row top-W; a banned token is a -inf logit, so lse and the scores
+    are those of the distribution renormalised over what is left. Finished hypotheses are left alone."""
+
+    def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False,
+                 constraints=None):
         super().__init__()
         if not 1 <= beam_size <= 8:
             raise ValueError("BeamSearchGenerator: beam_size must be in [1, 8]")
@@ -659,6 +770,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         self.eos_id = eos_id
         self.start_pos = BOS
         self._init_stepped(graph, beam=beam_size)
+        self.constraints = constraints
 
     def forward(self, data, return_all=False):
         m = self.model
@@ -677,7 +789,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
             raise ValueError("BeamSearchGenerator: the target vocabulary is smaller than the beam")
         with torch.no_grad():
             if self.graph and enc.is_cuda:
-                e = self._graph_entry(enc, src_mask, (self.beam_size,))
+                e = self._graph_entry(enc, src_mask, (self.beam_size, *self._constraint_key()))
                 for _ in range(self.max_tgt_len - 1):
                     e.graph.replay()
             else:
@@ -700,7 +812,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), cum=z(R, dtype=torch.float32),
                                fin=z(R, dtype=torch.uint8), t_dev=z(1, dtype=torch.int32),
                                lse=z(R, dtype=torch.float32), topv=z(R, W, dtype=torch.float32),
-                               topi=z(R, W, dtype=torch.int32))
+                               topi=z(R, W, dtype=torch.int32), suppress=self._suppress_state(dev))
 
     def _reset(self, e):
         """Step 0 of a new batch: BOS everywhere, one live hypothesis per AST. The self-attention cache needs no
@@ -722,6 +834,8 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         x = m.tgt_embedding.step(e.ys, e.t_dev)
         dec = m.decoder.step(x, e.cache, e.t_dev)
         logits = m.generator.linear(dec[:, 0])
+        if self.constraints is not None:  # a finished hypothesis offers (cum, PAD) whatever its logits: left alone
+            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
         beam_row_topk(logits, self.beam_size, e.lse, e.topv, e.topi, t_dev=e.t_dev, t_end=T - 1)
         beam_select(e.topv, e.topi, e.lse, e.cum, e.fin, e.ys, e.cache.pad, e.cache.anc, e.t_dev, eos_id=self.eos_id,
                     pad_id=PAD)
@@ -745,6 +859,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         from ._lib import lib
         if not lib().csa_beam_supported(self.beam_size, self.max_tgt_len) or enc.dtype != torch.float32:
             raise ValueError("BeamSearchGenerator: graph=True needs fp32 and max_tgt_len <= 256 (csa_beam_supported)")
+        self._check_constraints_capture(enc)
 
 
 class SamplingGenerator(_SteppedDecoding, nn.Module):
@@ -771,10 +886,14 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
     graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
     (..., temperature, top_k, top_p, num_samples, eos_id, return_logp, ...) (_SteppedDecoding); the seed lives in a
     16-byte device buffer filled outside the graph, so a replay draws anew. Bitwise the eager result. Inference only:
-    a model in training mode raises."""
+    a model in training mode raises.
+
+    constraints=DecodingConstraints(...): every live row's logits go through decode_ops.constrain_rows before
+    sample_rows, which never draws a -inf entry and renormalises: logp is the log-probability under the constrained,
+    filtered distribution. Finished rows are left alone."""
 
     def __init__(self, model, max_tgt_len, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, eos_id=EOS,
-                 multi_gpu=False, graph=False):
+                 multi_gpu=False, graph=False, constraints=None):
         super().__init__()
         if not float(temperature) > 0.0:
             raise ValueError("SamplingGenerator: temperature must be positive")
@@ -793,6 +912,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         self.eos_id = eos_id
         self.start_pos = BOS
         self._init_stepped(graph, group=self.num_samples)
+        self.constraints = constraints
 
     def forward(self, data, seed=None, return_logp=False):
         m = self.model
@@ -814,7 +934,8 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         T = self.max_tgt_len
         with torch.no_grad():
             if self.graph and enc.is_cuda:
-                extras = (self.temperature, self.top_k, self.top_p, self.num_samples, self.eos_id, return_logp)
+                extras = (self.temperature, self.top_k, self.top_p, self.num_samples, self.eos_id, return_logp,
+                          *self._constraint_key())
                 e = self._graph_entry(enc, src_mask, extras, return_logp=return_logp)
                 e.rng.copy_(key)  # outside the graph: the replays read it on the device
                 for _ in range(T - 1):
@@ -841,7 +962,8 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
         return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), fin=z(R, dtype=torch.uint8),
                                t_dev=z(1, dtype=torch.int32), rng=z(2, dtype=torch.int64),
-                               logp=z(R, T - 1, dtype=torch.float32) if return_logp else None)
+                               logp=z(R, T - 1, dtype=torch.float32) if return_logp else None,
+                               suppress=self._suppress_state(dev))
 
     def _reset(self, e):
         """Step 0 of a new batch: BOS everywhere, no row finished. The self-attention cache needs no reset (rows above t
@@ -862,6 +984,8 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         x = m.tgt_embedding.step(e.ys, e.t_dev)
         dec = m.decoder.step(x, e.cache, e.t_dev)
         logits = m.generator.linear(dec[:, 0])
+        if self.constraints is not None:  # a finished row takes PAD whatever its logits: left alone
+            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
         sample_rows(logits, e.ys, e.cache.pad, e.fin, e.t_dev, e.rng, temperature=self.temperature, top_k=self.top_k,
                     top_p=self.top_p, eos_id=self.eos_id, pad_id=PAD, logp=e.logp)
         e.t_dev.add_(1)
@@ -872,6 +996,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         if not lib().csa_sample_rows_supported(V) or enc.dtype != torch.float32:
             raise ValueError("SamplingGenerator: graph=True needs fp32 and a target vocabulary of at most 32768 "
                              "(csa_sample_rows_supported)")
+        self._check_constraints_capture(enc)
 
 
 class _GatherTargets(torch.autograd.Function):

@@ -409,6 +409,35 @@ typedef struct csa_sample_rows_args {
 int csa_sample_rows_supported(int64_t V);
 csa_status csa_sample_rows(const csa_sample_rows_args* a, void* stream);
 
+/* ---- v10 additions: decoding constraints (repetition penalty, n-gram, length and token bans) on that step ----
+ * Rewrites the (rows, V) fp32 last-position logits IN PLACE, between the generator's linear and whichever selection
+ * follows (csa_argmax_rows_step, csa_beam_row_topk, csa_sample_rows), which see a banned token as a -inf logit and
+ * renormalise over what is left. 2 <= T <= 1024 (csa_constrain_rows_supported); V is not limited. The step t is read
+ * from t_dev, or is the host value a->t when t_dev is NULL; a t outside [0, T - 1) makes the launch store nothing and
+ * read no row, and so does fin[r] != 0 for its row (fin may be NULL: no row is finished). Per row r, with the history
+ * h[0 .. L) = ys[r, 0 .. t], L = t + 1, the literal token columns (BOS included, PAD and EOS as any other id; an id
+ * outside [0, V) takes part in every comparison and is never written):
+ *   repetition_penalty theta (1: off): for every DISTINCT in-range token v of h, once however often it occurs,
+ *     z_v = z_v > 0 ? fl32(z_v / theta) : fl32(z_v * theta), one correctly rounded fp32 operation each, so 0, -inf and
+ *     NaN map to themselves;
+ *   no_repeat_ngram n (0: off): for every i in [0, L - n] with h[i + k] == h[L - (n - 1) + k] for all 0 <= k < n - 1,
+ *     token h[i + n - 1] is banned (n = 1 bans every history token; L < n bans nothing);
+ *   min_length: eos_id is banned while t < min_length (off when eos_id < 0 or min_length == 0);
+ *   suppress: every in-range id of the device list (at most 256 entries) is banned at every step.
+ * A ban stores -inf and wins over the penalty. Nothing else in the row is read or written. Deterministic, no atomics,
+ * no allocation, no sync: capturable. */
+typedef struct csa_constrain_rows_args {
+  float* logits; int64_t rows, V, logits_stride;   /* in / out, row stride >= V */
+  const int64_t* ys; int64_t ys_stride, T;          /* (rows, T) token buffer, row stride >= T */
+  const uint8_t* fin;                               /* (rows) or NULL */
+  float repetition_penalty;                         /* in (0, inf); 1 = off */
+  int64_t no_repeat_ngram, min_length, eos_id;
+  const int32_t* suppress; int64_t n_suppress;      /* device list, <= 256, or NULL / 0 */
+  int64_t t; const int32_t* t_dev;                  /* t_dev NULL: the host value t */
+} csa_constrain_rows_args;
+int csa_constrain_rows_supported(int64_t T);
+csa_status csa_constrain_rows(const csa_constrain_rows_args* a, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);
