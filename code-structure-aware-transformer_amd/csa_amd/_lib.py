@@ -274,6 +274,10 @@ def lib():
     L.csa_decode_embed.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, f32, vp, i64, vp]
     L.csa_argmax_rows_step.restype = ctypes.c_int
     L.csa_argmax_rows_step.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, i64, vp, vp]
+    L.csa_argmax_rows_fin_step.restype = ctypes.c_int  # v10 additions: early stop at EOS
+    L.csa_argmax_rows_fin_step.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp]
+    L.csa_decode_advance.restype = ctypes.c_int
+    L.csa_decode_advance.argtypes = [vp, i64, i64, vp, vp, vp]
     L.csa_beam_supported.restype = ctypes.c_int  # v10 additions: beam search over the device-stepped step
     L.csa_beam_supported.argtypes = [i64, i64]
     L.csa_beam_row_topk.restype = ctypes.c_int
@@ -319,6 +323,7 @@ EXPORTED_SYMBOLS = (
     "csa_collate_relations",
     "csa_decode_attn_supported", "csa_decode_attn", "csa_argmax_rows",
     "csa_decode_attn_step", "csa_decode_embed", "csa_argmax_rows_step",
+    "csa_argmax_rows_fin_step", "csa_decode_advance",
     "csa_beam_supported", "csa_beam_row_topk", "csa_beam_select", "csa_decode_attn_beam",
     "csa_sample_rows_supported", "csa_sample_rows",
     "csa_constrain_rows_supported", "csa_constrain_rows",

@@ -20,7 +20,12 @@ torch fallback restates the same rule, Philox included, in integer tensor ops.
 
 Decoding constraints (csrc/csa_constrain.hip): constrain_rows rewrites the logits in place in front of any of the three
 selections (repetition penalty, no-repeat n-gram, minimum length, suppressed ids); its torch fallback is bitwise the
-kernel."""
+kernel.
+
+Early stop at EOS (csrc/csa_decode.hip): argmax_rows(..., fin=, eos_id=) is the device-stepped argmax with a finished
+flag per row (csa_argmax_rows_fin_step) and decode_advance ends a step in place of the counter's increment: it counts
+the step and parks the counter at -1 once every row has finished (csa_decode_advance); both fallbacks are bitwise the
+kernels."""
 import ctypes
 
 import torch
@@ -200,7 +205,7 @@ def _head_view(head_pad, rows):
     return head_pad.view(head_pad.shape[1], rows, head_pad.shape[2])
 
 
-def _argmax_rows_step(x, ys, pad, pad_id, t_dev, head_pad):
+def _argmax_rows_step(x, ys, pad, pad_id, t_dev, head_pad, fin=None, eos_id=None):
     rows, V = x.shape
     T = ys.shape[1] if ys.dim() == 2 else -1
     if (ys.dtype != torch.int64 or ys.dim() != 2 or ys.shape[0] != rows or ys.stride(1) != 1 or ys.device != x.device
@@ -211,35 +216,87 @@ def _argmax_rows_step(x, ys, pad, pad_id, t_dev, head_pad):
                                           or not head_pad.is_contiguous() or head_pad.device != x.device))):
         raise ValueError("argmax_rows: with t_dev, out is the (rows, T) int64 token buffer, is_pad (rows, T) uint8, both "
                          "with a contiguous last dim, and head_pad (rows, H, T) uint8 contiguous")
+    if fin is not None and (fin.dtype != torch.uint8 or fin.shape != (rows,) or not fin.is_contiguous()
+                            or fin.device != x.device):
+        raise ValueError("argmax_rows: fin is a (rows,) uint8 contiguous tensor on x's device")
     _check_step(t_dev, x.device, "argmax_rows")
+    eos = -1 if eos_id is None else int(eos_id)
     if _rows_hip_ok(x):
+        tail = (_ptr(pad), pad.stride(0) if pad is not None else 0, _ptr(head_pad),
+                head_pad.shape[1] if head_pad is not None else 0, pad_id)
         with on_device(x.device):
-            check(lib().csa_argmax_rows_step(_ptr(x), rows, V, _ptr(ys), ys.stride(0), T, _ptr(pad),
-                                             pad.stride(0) if pad is not None else 0, _ptr(head_pad),
-                                             head_pad.shape[1] if head_pad is not None else 0, pad_id, _ptr(t_dev),
-                                             _stream(x.device)), "csa_argmax_rows_step")
+            if fin is None:
+                check(lib().csa_argmax_rows_step(_ptr(x), rows, V, _ptr(ys), ys.stride(0), T, *tail, _ptr(t_dev),
+                                                 _stream(x.device)), "csa_argmax_rows_step")
+            else:
+                check(lib().csa_argmax_rows_fin_step(_ptr(x), rows, V, _ptr(ys), ys.stride(0), T, *tail, _ptr(fin), eos,
+                                                     _ptr(t_dev), _stream(x.device)), "csa_argmax_rows_fin_step")
         return ys
     col = _step_value(t_dev, 0, T - 1, "argmax_rows") + 1  # column in [1, T)
     _argmax_rows_ref(x, ys[:, col], None if pad is None else pad[:, col], pad_id, None)
+    if fin is not None:  # a finished row takes PAD; a live row that drew eos_id is finished from the next step on
+        done = fin != 0
+        ys[:, col].masked_fill_(done, pad_id)
+        if pad is not None:
+            pad[:, col] = ys[:, col] == pad_id
+        fin.masked_fill_(~done & (ys[:, col] == eos), 1)
     if head_pad is not None:
         _head_view(head_pad, rows)[:, :, col] = ys[:, col] == pad_id
     return ys
 
 
-def argmax_rows(x, out=None, is_pad=None, pad_id=0, maxval=None, t_dev=None, head_pad=None):
+def decode_advance(fin, t_dev, state, T):
+    """The end of an early-stopping decode step, in place of the counter's increment (csa_decode_advance,
+    include/csa_hip.h). fin (R,) uint8, any non-zero byte = finished, a contiguous view of any alignment; t_dev the
+    1-element int32 step counter; state (4,) int32 = {all_prev, steps_run, parked, reserved}, zeroed before step 0; T the
+    token buffer's columns. Parked: nothing changes. Otherwise steps_run += 1 and the counter parks at -1 (parked = 1)
+    when all_prev is set or step t was the last (t + 1 >= T - 1), else moves to t + 1 with all_prev = every row finished.
+    The step kernels store nothing for a negative counter, so a parked step is harmless. CUDA tensors run the kernel;
+    CPU tensors run the same rule on the host."""
+    dev = t_dev.device
+    _check_step(t_dev, dev, "decode_advance")
+    if (fin.dtype != torch.uint8 or fin.dim() != 1 or (fin.numel() > 1 and fin.stride(0) != 1) or fin.device != dev
+            or state.dtype != torch.int32 or state.shape != (4,) or not state.is_contiguous() or state.device != dev):
+        raise ValueError("decode_advance: fin (R,) uint8 with unit stride and state (4,) int32 contiguous, both on the "
+                         "counter's device")
+    T = int(T)
+    if T < 2:
+        raise ValueError("decode_advance: T >= 2")
+    if dev.type == "cuda":
+        with on_device(dev):
+            check(lib().csa_decode_advance(_ptr(fin), fin.numel(), T, _ptr(t_dev), _ptr(state), _stream(dev)),
+                  "csa_decode_advance")
+        return
+    all_prev, steps, parked, _ = state.tolist()
+    if parked:
+        return
+    t = int(t_dev.item())
+    state[1] = steps + 1
+    if all_prev or t + 1 >= T - 1:
+        t_dev.fill_(-1)
+        state[2] = 1
+    else:
+        t_dev.fill_(t + 1)
+        state[0] = int(bool((fin != 0).all()))
+
+
+def argmax_rows(x, out=None, is_pad=None, pad_id=0, maxval=None, t_dev=None, head_pad=None, fin=None, eos_id=None):
     """Row argmax of x (rows, V) into `out` (rows,) int64, which may be a strided column such as ys[:, t+1];
     ties go to the lowest index. Optionally is_pad (rows,) uint8 (strided) receives (index == pad_id) and maxval
     (rows,) fp32 contiguous the row maximum. Returns out.
     Device-stepped (t_dev a 1-element int32 tensor): out is the whole (rows, T) token buffer and is_pad the whole
     (rows, T) mask; the kernel reads t and writes column t + 1 of both and, when head_pad (rows, H, T) is given, the
     same byte into head_pad.view(H, rows, T)[:, r, t + 1], the column BaseDecoder.step would copy from is_pad at the
-    top of step t + 1. A column outside [1, T) stores nothing."""
+    top of step t + 1. A column outside [1, T) stores nothing.
+    fin (rows,) uint8 with eos_id, device-stepped only (csa_argmax_rows_fin_step): a row with fin != 0 takes pad_id and
+    PAD byte 1 in is_pad and head_pad whatever its logits; a live row whose argmax is eos_id (None: never) gets
+    fin = 1, so it is finished from the next step on."""
     if t_dev is not None:
         if out is None or maxval is not None:
             raise ValueError("argmax_rows: with t_dev, out is required and maxval is not available")
-        return _argmax_rows_step(x, out, is_pad, pad_id, t_dev, head_pad)
-    if head_pad is not None:
-        raise ValueError("argmax_rows: head_pad goes with t_dev")
+        return _argmax_rows_step(x, out, is_pad, pad_id, t_dev, head_pad, fin, eos_id)
+    if head_pad is not None or fin is not None:
+        raise ValueError("argmax_rows: head_pad and fin go with t_dev")
     rows, _ = x.shape
     if out is None:
         out = torch.empty(rows, dtype=torch.int64, device=x.device)

@@ -532,16 +532,108 @@ class _SteppedDecoding:
 
     constraints= (a DecodingConstraints) is shared by the three generators: when active, one decode_ops.constrain_rows
     call sits between generator.linear and the selection of every step, the value joins the graph key extras and the
-    suppress list is a static device tensor of the state; None or an inactive value changes nothing."""
+    suppress list is a static device tensor of the state; None or an inactive value changes nothing.
+
+    early_stop=True (needs an eos_id, so a finished flag e.fin per row) is one rule for the three generators: decoding
+    stops after the first step that BEGAN with every row finished, one step after the step s that finished the last
+    row, so steps 0..s+1 run; without such a step all max_tgt_len - 1 run. The extra step is the one after which the
+    state is a fixed point (for the beam, the step in which the selection orders the all-finished hypotheses by cum), so
+    ids, scores and log-probabilities are bitwise those of the full run; columns never written stay PAD / 0 as _reset
+    leaves them. On the device the rule is a latch: the step ends with decode_ops.decode_advance in place of the
+    counter's increment, which counts the step in the state words e.stop = {all_prev, steps_run, parked, 0} and parks
+    the counter at -1; every step kernel returns on a negative counter, so a surplus replay stores nothing. The host
+    (_run_steps) issues replays in chunks of poll_every, copies the state words to a pinned buffer after each chunk
+    (outside the graph, same stream, non-blocking) and, before issuing chunk k + 2, waits for chunk k's copy and stops
+    if it reports parked: at most two chunks are ever in flight and no kernel waits on the host. last_steps_run is the
+    latch's count after the call (max_tgt_len - 1 without early_stop), exact whatever the chunking; last_replays is
+    the number of steps issued, at most last_steps_run + 2 * poll_every. False keeps the launches, the graph key and
+    the captured graph of a generator built without the keyword."""
 
     MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
+    POLL_EVERY = 2  # replays per chunk of an early-stopping graph=True call: the fastest of 2, 4 and 8
+                    # (tools/bench_early_stop.py, profiles/early_stop_decode.json)
 
-    def _init_stepped(self, graph, **cache_options):
+    def _init_stepped(self, graph, early_stop=False, **cache_options):
         self.graph = graph
         self.captures = 0      # graphs captured so far (graph=True on a CUDA model; 0 otherwise)
         self._graphs = {}      # key -> SimpleNamespace of static buffers and the captured step (insertion-ordered)
         self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
         self._cache_options = cache_options  # what the generator asks of BaseDecoder.empty_cache
+        self.early_stop = bool(early_stop)
+        self.poll_every = self.POLL_EVERY
+        self.last_steps_run = None  # decode steps that ran in the last call
+        self.last_replays = None    # decode steps issued in the last call (>= last_steps_run: parked ones store nothing)
+        self._check_early_stop()
+
+    def _check_early_stop(self):
+        if self.early_stop and self.eos_id is None:
+            raise ValueError(f"{type(self).__name__}: early_stop=True needs an eos_id (without one no row ever finishes)")
+
+    def _stop_key(self):
+        """What early_stop adds to the graph key extras: nothing when it is off."""
+        return ("early_stop",) if self.early_stop else ()
+
+    def _stop_state(self, device):
+        """The latch's state words {all_prev, steps_run, parked, reserved} of a step's state (None without early_stop)."""
+        return torch.zeros(4, dtype=torch.int32, device=device) if self.early_stop else None
+
+    def _advance(self, e):
+        """The end of a device step, after the counter's last reader: the increment, or the early-stop latch."""
+        if e.stop is None:
+            e.t_dev.add_(1)
+        else:
+            from .decode_ops import decode_advance
+            decode_advance(e.fin, e.t_dev, e.stop, self.max_tgt_len)
+
+    def _run_steps(self, e, graphed, after_step=None):
+        """The decode steps of one call on the reset state e: replays of e.graph (graphed) or eager _device_step calls,
+        max_tgt_len - 1 of them or, with early_stop, until the latch reports parked (see the class docstring).
+        after_step() runs on the host after each issued step. Sets last_steps_run and last_replays."""
+        self._check_early_stop()
+        n = self.max_tgt_len - 1
+        step = e.graph.replay if graphed else (lambda: self._device_step(e))
+        if e.stop is None:
+            for _ in range(n):
+                step()
+                if after_step is not None:
+                    after_step()
+            self.last_steps_run = self.last_replays = n
+            return
+        issued = 0
+        if not graphed:  # host-bound already: read the latch after every step
+            while issued < n:
+                step()
+                issued += 1
+                if after_step is not None:
+                    after_step()
+                if int(e.stop[2]) != 0:
+                    break
+            self.last_steps_run, self.last_replays = int(e.stop[1]), issued
+            return
+        poll = max(1, int(self.poll_every))
+        chunks = (n + poll - 1) // poll
+        if e.stop_host is None or e.stop_host.shape[0] < chunks + 1:
+            e.stop_host = torch.empty(chunks + 1, 4, dtype=torch.int32, pin_memory=True)
+        stream = torch.cuda.current_stream(e.stop.device)
+        events = []
+        while issued < n:
+            k = len(events)
+            if k >= 2:  # chunks k - 1 and k - 2 are in flight: wait for the older one's state words
+                events[k - 2].synchronize()
+                if int(e.stop_host[k - 2, 2]) != 0:
+                    break
+            for _ in range(min(poll, n - issued)):
+                step()
+                issued += 1
+                if after_step is not None:
+                    after_step()
+            e.stop_host[k].copy_(e.stop, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            events.append(ev)
+        e.stop_host[chunks].copy_(e.stop, non_blocking=True)
+        stream.synchronize()
+        self.last_steps_run, self.last_replays = int(e.stop_host[chunks, 1]), issued
 
     @property
     def constraints(self):
@@ -628,8 +720,8 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
     encoder memory (csa_decode_attn), the Generator's linear on the B last rows, and the row argmax written into
     ys[:, t+1] with the next step's PAD byte (csa_argmax_rows). Eval-mode log(softmax(z)) is monotone in z, so the
     argmax of the logits is the reference's torch.max(out, 1)[1] and the softmax is skipped unless return_logp asks for
-    the (max_tgt_len-1, B, V) last-position log-probabilities. All max_tgt_len-1 steps always run (no early stop at
-    EOS), as in the reference. In training mode this defers to GreedyGenerator.
+    the (max_tgt_len-1, B, V) last-position log-probabilities. All max_tgt_len-1 steps run, as in the reference, unless
+    early_stop asks otherwise (below). In training mode this defers to GreedyGenerator.
 
     graph=True (eval mode, CUDA model): the loop above is bound by the host, about 70 small launches per step issued
     from Python. The step is instead run device-stepped (csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step)
@@ -640,20 +732,30 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
     constraints=DecodingConstraints(...): the logits of every step go through decode_ops.constrain_rows before the
     argmax (history = the row's tokens so far, BOS included; there is no finished flag here, so the rules keep applying
     after an EOS), and return_logp reports the constrained distribution. Training mode with active constraints
-    raises: the uncached loop it defers to has no such step."""
+    raises: the uncached loop it defers to has no such step.
 
-    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False, constraints=None):
+    eos_id (default None: the behaviour above, bit for bit): the generator keeps a finished flag per row, fin (B,) uint8.
+    A row that has emitted eos_id takes PAD from then on (csa_argmax_rows_fin_step) and active constraints leave it
+    alone. With the head-repeated PAD mask a finished row's PAD columns enter other rows' masks, so this is a behaviour
+    of its own, not a truncation of the ids without eos_id. early_stop=True (needs eos_id; _SteppedDecoding) stops the
+    call once every row has finished, with the ids of the full run, and return_logp then returns the steps that ran,
+    (last_steps_run, B, V). Training mode with an eos_id raises."""
+
+    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False, constraints=None, eos_id=None,
+                 early_stop=False):
         super().__init__(model, max_tgt_len, multi_gpu)
-        self._init_stepped(graph, repeat_heads=True)  # as CSATrans.decode masks
+        self.eos_id = eos_id
+        self._init_stepped(graph, early_stop, repeat_heads=True)  # as CSATrans.decode masks
         self.constraints = constraints
 
     def forward(self, data, return_logp=False):
         m = self.model
         if m.training:
-            if self.constraints is not None:
-                raise RuntimeError("CachedGreedyGenerator: constraints are for inference only (the uncached loop that "
-                                   "training mode defers to has no constraint step)")
+            if self.constraints is not None or self.eos_id is not None:
+                raise RuntimeError("CachedGreedyGenerator: constraints and eos_id are for inference only (the uncached "
+                                   "loop that training mode defers to has neither)")
             ys = super().forward(data)
+            self.last_steps_run = self.last_replays = self.max_tgt_len - 1
             return (ys, None) if return_logp else ys
         from .decode_ops import argmax_rows
         from .gen_ops import gen_log_softmax
@@ -663,6 +765,10 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
             if self.graph and enc.is_cuda:
                 return self._forward_graph(data, enc, return_logp)
             B, T = enc.size(0), self.max_tgt_len
+            if self.eos_id is not None:  # the device-stepped step run eagerly, as the other two generators do
+                e = self._state(m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True), bool(return_logp))
+                self._reset(e)
+                return self._decode(e, False)
             cache = m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True)  # as CSATrans.decode masks
             ys = torch.zeros(B, T, dtype=torch.long, device=enc.device)
             ys[:, 0] = self.start_pos
@@ -678,6 +784,7 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
                 argmax_rows(logits, out=ys[:, t + 1], is_pad=cache.pad[:, t + 1], pad_id=PAD)
                 if return_logp:
                     logps.append(gen_log_softmax(logits, 0.0))
+            self.last_steps_run = self.last_replays = T - 1
             out = ys[:, 1:]
             return (out, torch.stack(logps)) if return_logp else out
 
@@ -689,7 +796,9 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
         B, T = cache.pad.shape
         z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=cache.pad.device)
         return SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None,
-                               return_logp=return_logp, suppress=self._suppress_state(cache.pad.device))
+                               return_logp=return_logp, suppress=self._suppress_state(cache.pad.device),
+                               fin=z(B, dtype=torch.uint8) if self.eos_id is not None else None,
+                               stop=self._stop_state(cache.pad.device), stop_host=None)
 
     def _device_step(self, e):
         """One decode step with every step-dependent index read from e.t_dev on the device: the same launches for
@@ -700,11 +809,15 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
         x = m.tgt_embedding.step(e.ys, e.t_dev)
         dec = m.decoder.step(x, e.cache, e.t_dev)
         logits = m.generator.linear(dec[:, 0])
-        if self.constraints is not None:
-            self.constraints.apply(logits, e.ys, e.t_dev, suppress=e.suppress)
-        argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
+        if self.constraints is not None:  # with eos_id, a finished row takes PAD whatever its logits: left alone
+            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
+        if e.fin is None:
+            argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
+        else:
+            argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad,
+                        fin=e.fin, eos_id=self.eos_id)
         e.logp = gen_log_softmax(logits, 0.0) if e.return_logp else None
-        e.t_dev.add_(1)
+        self._advance(e)
 
     def _reset(self, e):
         """Step 0 of a new batch. The self-attention cache needs no reset: rows above t are never read."""
@@ -712,25 +825,36 @@ class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
         e.ys[:, 0] = self.start_pos
         e.cache.pad.zero_()
         e.cache.head_pad.zero_()
+        if e.fin is not None:
+            e.fin.zero_()
+        if e.stop is not None:
+            e.stop.zero_()
         e.t_dev.zero_()
+
+    def _eos_key(self):
+        """What eos_id adds to the graph key extras: nothing without one."""
+        return () if self.eos_id is None else ("eos", int(self.eos_id))
 
     def _forward_graph(self, data, enc, return_logp):
         return_logp = bool(return_logp)
-        e = self._graph_entry(enc, data.src_mask, (return_logp, *self._constraint_key()), return_logp=return_logp)
+        extras = (return_logp, *self._constraint_key(), *self._eos_key(), *self._stop_key())
+        return self._decode(self._graph_entry(enc, data.src_mask, extras, return_logp=return_logp), True)
+
+    def _decode(self, e, graphed):
+        """The steps of one call on the reset state e; each step's log-probabilities are copied out of their slot as
+        the step is issued, and those of the steps that ran are returned."""
         logps = []
-        for _ in range(self.max_tgt_len - 1):
-            e.graph.replay()
-            if return_logp:
-                logps.append(e.logp.clone())
+        self._run_steps(e, graphed, (lambda: logps.append(e.logp.clone())) if e.return_logp else None)
         out = e.ys[:, 1:].clone()
-        return (out, torch.stack(logps)) if return_logp else out
+        return (out, torch.stack(logps[:self.last_steps_run])) if e.return_logp else out
 
 
 class BeamSearchGenerator(_SteppedDecoding, nn.Module):
     """Beam search of width W = beam_size over the KV-cached, device-stepped decode step (no counterpart in the
     reference, whose only strategy is GreedyGenerator).
 
-    Rows are R = B * W hypotheses, row r = b * W + w. All max_tgt_len - 1 steps run (no early stop, static shapes).
+    Rows are R = B * W hypotheses, row r = b * W + w. All max_tgt_len - 1 steps run (static shapes) unless
+    early_stop=True (_SteppedDecoding) ends the call once every hypothesis has finished; the result is bitwise the same.
     cum (fp32) starts at 0 for row b * W and -inf for the other W - 1 rows, all tokens BOS. Per step the eval-mode
     generator logits z give logp = z - lse (fp32) and a candidate scores cum[r] + (z - lse[r]); a hypothesis that has
     emitted eos_id is finished (None: never), offers the single candidate (cum, PAD), and its row still runs through
@@ -757,7 +881,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
     are those of the distribution renormalised over what is left. Finished hypotheses are left alone."""
 
     def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False,
-                 constraints=None):
+                 constraints=None, early_stop=False):
         super().__init__()
         if not 1 <= beam_size <= 8:
             raise ValueError("BeamSearchGenerator: beam_size must be in [1, 8]")
@@ -769,7 +893,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         self.length_penalty = float(length_penalty)
         self.eos_id = eos_id
         self.start_pos = BOS
-        self._init_stepped(graph, beam=beam_size)
+        self._init_stepped(graph, early_stop, beam=beam_size)
         self.constraints = constraints
 
     def forward(self, data, return_all=False):
@@ -789,15 +913,13 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
             raise ValueError("BeamSearchGenerator: the target vocabulary is smaller than the beam")
         with torch.no_grad():
             if self.graph and enc.is_cuda:
-                e = self._graph_entry(enc, src_mask, (self.beam_size, *self._constraint_key()))
-                for _ in range(self.max_tgt_len - 1):
-                    e.graph.replay()
+                e = self._graph_entry(enc, src_mask, (self.beam_size, *self._constraint_key(), *self._stop_key()))
+                self._run_steps(e, True)
             else:
                 cache = self.model.decoder.make_cache(enc, src_mask, self.max_tgt_len, beam=self.beam_size)
                 e = self._state(cache)
                 self._reset(e)
-                for _ in range(self.max_tgt_len - 1):
-                    self._device_step(e)
+                self._run_steps(e, False)
             return self._rank(e, enc.size(0), return_all)
 
     def _check_eval(self):
@@ -812,7 +934,8 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), cum=z(R, dtype=torch.float32),
                                fin=z(R, dtype=torch.uint8), t_dev=z(1, dtype=torch.int32),
                                lse=z(R, dtype=torch.float32), topv=z(R, W, dtype=torch.float32),
-                               topi=z(R, W, dtype=torch.int32), suppress=self._suppress_state(dev))
+                               topi=z(R, W, dtype=torch.int32), suppress=self._suppress_state(dev),
+                               stop=self._stop_state(dev), stop_host=None)
 
     def _reset(self, e):
         """Step 0 of a new batch: BOS everywhere, one live hypothesis per AST. The self-attention cache needs no
@@ -824,6 +947,8 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         e.cum.fill_(float("-inf"))
         e.cum.view(-1, self.beam_size)[:, 0] = 0.0
         e.fin.zero_()
+        if e.stop is not None:
+            e.stop.zero_()
         e.t_dev.zero_()
 
     def _device_step(self, e):
@@ -839,7 +964,7 @@ class BeamSearchGenerator(_SteppedDecoding, nn.Module):
         beam_row_topk(logits, self.beam_size, e.lse, e.topv, e.topi, t_dev=e.t_dev, t_end=T - 1)
         beam_select(e.topv, e.topi, e.lse, e.cum, e.fin, e.ys, e.cache.pad, e.cache.anc, e.t_dev, eos_id=self.eos_id,
                     pad_id=PAD)
-        e.t_dev.add_(1)
+        self._advance(e)
 
     def _rank(self, e, B, return_all):
         W, T = self.beam_size, self.max_tgt_len
@@ -875,7 +1000,8 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
     temperature, top-k with all ties, top-p on the renormalised top-k set (tie-inclusive), one Gumbel-max draw from
     Philox stream 7 keyed by (seed, row, step, column), logp = y[token] - lse(y over the kept set). A row that has
     emitted eos_id is finished (None: never): it takes PAD with logp 0 and still runs through the decoder, ignored.
-    All max_tgt_len - 1 steps run (no early stop, static shapes).
+    All max_tgt_len - 1 steps run (static shapes) unless early_stop=True (_SteppedDecoding) ends the call once every row
+    has finished; ids and log-probabilities are bitwise the same.
 
     forward(data, seed=None, return_logp=False) / sample(enc, src_mask, seed, return_logp) return the ids
     (B, max_tgt_len - 1), or (B, num_samples, max_tgt_len - 1) when num_samples > 1, PAD after EOS; with return_logp
@@ -893,7 +1019,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
     filtered distribution. Finished rows are left alone."""
 
     def __init__(self, model, max_tgt_len, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, eos_id=EOS,
-                 multi_gpu=False, graph=False, constraints=None):
+                 multi_gpu=False, graph=False, constraints=None, early_stop=False):
         super().__init__()
         if not float(temperature) > 0.0:
             raise ValueError("SamplingGenerator: temperature must be positive")
@@ -911,7 +1037,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         self.num_samples = int(num_samples)
         self.eos_id = eos_id
         self.start_pos = BOS
-        self._init_stepped(graph, group=self.num_samples)
+        self._init_stepped(graph, early_stop, group=self.num_samples)
         self.constraints = constraints
 
     def forward(self, data, seed=None, return_logp=False):
@@ -935,18 +1061,16 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         with torch.no_grad():
             if self.graph and enc.is_cuda:
                 extras = (self.temperature, self.top_k, self.top_p, self.num_samples, self.eos_id, return_logp,
-                          *self._constraint_key())
+                          *self._constraint_key(), *self._stop_key())
                 e = self._graph_entry(enc, src_mask, extras, return_logp=return_logp)
                 e.rng.copy_(key)  # outside the graph: the replays read it on the device
-                for _ in range(T - 1):
-                    e.graph.replay()
+                self._run_steps(e, True)
             else:
                 cache = self.model.decoder.make_cache(enc, src_mask, T, group=self.num_samples)
                 e = self._state(cache, return_logp)
                 self._reset(e)
                 e.rng.copy_(key)
-                for _ in range(T - 1):
-                    self._device_step(e)
+                self._run_steps(e, False)
             shape = (enc.size(0), T - 1) if self.num_samples == 1 else (enc.size(0), self.num_samples, T - 1)
             ids = e.ys[:, 1:].reshape(shape).clone()
             return (ids, e.logp.reshape(shape).clone()) if return_logp else ids
@@ -963,7 +1087,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), fin=z(R, dtype=torch.uint8),
                                t_dev=z(1, dtype=torch.int32), rng=z(2, dtype=torch.int64),
                                logp=z(R, T - 1, dtype=torch.float32) if return_logp else None,
-                               suppress=self._suppress_state(dev))
+                               suppress=self._suppress_state(dev), stop=self._stop_state(dev), stop_host=None)
 
     def _reset(self, e):
         """Step 0 of a new batch: BOS everywhere, no row finished. The self-attention cache needs no reset (rows above t
@@ -974,6 +1098,8 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
         e.fin.zero_()
         if e.logp is not None:
             e.logp.zero_()
+        if e.stop is not None:
+            e.stop.zero_()
         e.t_dev.zero_()
 
     def _device_step(self, e):
@@ -988,7 +1114,7 @@ class SamplingGenerator(_SteppedDecoding, nn.Module):
             self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
         sample_rows(logits, e.ys, e.cache.pad, e.fin, e.t_dev, e.rng, temperature=self.temperature, top_k=self.top_k,
                     top_p=self.top_p, eos_id=self.eos_id, pad_id=PAD, logp=e.logp)
-        e.t_dev.add_(1)
+        self._advance(e)
 
     def _check_capture(self, enc):
         from ._lib import lib

@@ -14,6 +14,12 @@
 //                       forward's row function (csa_ln_row.hpp): bitwise the gather + add + csa_layernorm_fwd
 // A counter outside its range makes the launch store nothing and read no row.
 //
+// Early stop at EOS (one finished flag per row, fin):
+//   k_argmax_rows_fin_step  k_argmax_rows_step in which a finished row takes PAD and a row that draws EOS finishes
+//   k_decode_advance        ends the step in place of the counter's increment: counts it and, once every row has
+//                           finished (or after the last step), parks the counter at -1, the value for which every
+//                           step kernel stores nothing, so replays issued after that are harmless
+//
 // Beam search (csa_decode_attn_beam) is the same kernel with BEAM = true, two uniform changes of addressing only:
 //   ancestry  (anc set, self-attention) key / value j < t of row r is read from cache row anc[r, j]: a hypothesis'
 //             history stays where its ancestors stored it and no cache row is ever moved; row (r, t) is stored as above;
@@ -289,6 +295,63 @@ __global__ __launch_bounds__(ARG_T) void k_argmax_rows_step(const float* __restr
   }
 }
 
+// k_argmax_rows_step with a finished flag per row: a row with fin != 0 takes pad_id and PAD byte 1 without reading its
+// logits (the branch is uniform over the row's workgroup, so no barrier is skipped by part of it); a live row whose
+// argmax is eos_id sets its flag. eos_id < 0: no token finishes a row.
+__global__ __launch_bounds__(ARG_T) void k_argmax_rows_fin_step(const float* __restrict__ x, int64_t V,
+                                                               int64_t* __restrict__ ys, int64_t ys_stride, int64_t T,
+                                                               uint8_t* __restrict__ pad, int64_t pad_stride,
+                                                               uint8_t* __restrict__ head_pad, int H, int64_t pad_id,
+                                                               uint8_t* __restrict__ fin, int64_t eos_id,
+                                                               const int32_t* __restrict__ t_dev) {
+  const int64_t col = (int64_t)*t_dev + 1;
+  if (col < 1 || col >= T) return;  // the whole grid, before the barrier
+  const int64_t row = blockIdx.x, rows = gridDim.x;
+  const bool done = fin[row] != 0;
+  float v = 0.f;
+  int64_t i = pad_id;
+  if (!done) argmax_row(x + row * V, V, (V % 4 == 0) && (((uintptr_t)x) & 15) == 0, v, i);
+  if (threadIdx.x == 0) {
+    const uint8_t p = (done || i == pad_id) ? 1 : 0;
+    ys[row * ys_stride + col] = i;
+    if (pad) pad[row * pad_stride + col] = p;
+    if (head_pad)
+      for (int h = 0; h < H; ++h) head_pad[((int64_t)h * rows + row) * T + col] = p;
+    if (!done && eos_id >= 0 && i == eos_id) fin[row] = 1;
+  }
+}
+
+// The end of an early-stopping decode step, in place of the counter's increment: one workgroup reduces the finished
+// flags to all_now (every byte of fin[0..R) non-zero) and thread 0 moves the latch st = {all_prev, steps_run, parked,
+// reserved}. Parked: nothing changes. Otherwise the step that just ran is counted and the counter either parks at -1
+// (this step began with every row finished, or it was the last one), which makes every later launch of the step store
+// nothing, or moves on. fin is read byte by byte (any alignment); the reduction is an OR, the same in any order.
+constexpr int ADV_T = 256;
+
+__global__ __launch_bounds__(ADV_T) void k_decode_advance(const uint8_t* __restrict__ fin, int64_t R, int64_t T,
+                                                         int32_t* __restrict__ t_dev, int32_t* __restrict__ st) {
+  __shared__ int live_w[ADV_T / 64];
+  bool live = false;
+  for (int64_t r = threadIdx.x; r < R; r += ADV_T) live |= fin[r] == 0;
+  const bool wave_live = __ballot(live) != 0;
+  if ((threadIdx.x & 63) == 0) live_w[threadIdx.x >> 6] = wave_live ? 1 : 0;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int any_live = 0;
+#pragma unroll
+  for (int k = 0; k < ADV_T / 64; ++k) any_live |= live_w[k];
+  if (st[2] != 0) return;
+  const int64_t t = *t_dev;
+  st[1] += 1;
+  if (st[0] != 0 || t + 1 >= T - 1) {
+    *t_dev = -1;
+    st[2] = 1;
+  } else {
+    *t_dev = (int32_t)(t + 1);
+    st[0] = any_live ? 0 : 1;
+  }
+}
+
 // x[b] = LayerNorm(W[ys[b, t]] + pe[t]) for the position t read from the device counter (Embeddings.step): one wave
 // per row, the gathered row in registers, normalised by the LayerNorm forward's own row function. pe may be null
 // (no positional term). A token id outside [0, vocab) is clamped; a t outside [0, t_end) stores nothing.
@@ -483,6 +546,45 @@ csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     csa::set_error("csa_argmax_rows_step: %s", hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+csa_status csa_argmax_rows_fin_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
+                                    uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
+                                    uint8_t* fin, int64_t eos_id, const int32_t* t_dev, void* stream) {
+  if (rows < 0 || V < 1 || rows > 0x7fffffff || T < 1 || ys_stride < T || (pad && pad_stride < T) ||
+      (head_pad && (H < 1 || H > 0x7fffffff)))
+    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: bad rows / V / T / strides / H");
+  if (!x || !ys || !fin || !t_dev) return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: null pointer");
+  if ((((uintptr_t)x) & 3) || (((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3))
+    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: misaligned pointer");
+  if (rows == 0) return CSA_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  hipLaunchKernelGGL(k_argmax_rows_fin_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad,
+                     pad_stride, head_pad, (int)H, pad_id, fin, eos_id, t_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_argmax_rows_fin_step: %s", hipGetErrorString(e));
+    return CSA_LAUNCH_FAILED;
+  }
+  return CSA_OK;
+}
+
+csa_status csa_decode_advance(const uint8_t* fin, int64_t rows, int64_t T, int32_t* t_dev, int32_t* state,
+                              void* stream) {
+  if (rows < 0 || T < 2) return dfail(CSA_INVALID_ARG, "csa_decode_advance: bad rows / T (rows >= 0, T >= 2)");
+  if (!t_dev || !state || (rows > 0 && !fin)) return dfail(CSA_INVALID_ARG, "csa_decode_advance: null pointer");
+  if ((((uintptr_t)t_dev) & 3) || (((uintptr_t)state) & 3))
+    return dfail(CSA_INVALID_ARG, "csa_decode_advance: misaligned pointer (t_dev and state 4 bytes; fin any)");
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  hipLaunchKernelGGL(k_decode_advance, dim3(1), dim3(ADV_T), 0, st, fin, rows, T, t_dev, state);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    csa::set_error("csa_decode_advance: %s", hipGetErrorString(e));
     return CSA_LAUNCH_FAILED;
   }
   return CSA_OK;

@@ -332,6 +332,28 @@ csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t
                                 uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
                                 const int32_t* t_dev, void* stream);
 
+/* ---- v10 additions: early stop at EOS for the device-stepped decode step ----
+ * csa_argmax_rows_fin_step: csa_argmax_rows_step with a finished flag per row, fin (rows) bytes. A row with
+ * fin[r] != 0 takes pad_id and PAD byte 1 (pad and every head of head_pad) whatever its logits; a live row takes its
+ * argmax as above and sets fin[r] = 1 when that is eos_id (eos_id < 0: never). fin is otherwise left as it is.
+ * Valid t + 1: [1, T), as csa_argmax_rows_step.
+ *
+ * csa_decode_advance: the end of a step, in place of the counter's increment. state is int32[4] = {all_prev,
+ * steps_run, parked, reserved}, zeroed by the caller before step 0; all_now = every byte of fin[0 .. rows) is non-zero
+ * (rows = 0: true). One workgroup, no atomics, no waiting:
+ *   parked != 0                         nothing changes;
+ *   otherwise                           steps_run += 1, then
+ *     all_prev != 0 or t + 1 >= T - 1   *t_dev = -1, parked = 1 (every step kernel stores nothing for t < 0);
+ *     else                              *t_dev = t + 1, all_prev = all_now.
+ * So the counter parks after the first step that BEGAN with every row finished, one step after the step that finished
+ * the last row, or after step T - 2; steps_run is then the number of steps that ran. fin may have any alignment; t_dev
+ * and state are 4-byte aligned. T >= 2. Neither entry point syncs or allocates. */
+csa_status csa_argmax_rows_fin_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
+                                    uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
+                                    uint8_t* fin, int64_t eos_id, const int32_t* t_dev, void* stream);
+csa_status csa_decode_advance(const uint8_t* fin, int64_t rows, int64_t T, int32_t* t_dev, int32_t* state,
+                              void* stream);
+
 /* ---- v10 additions: beam search over the device-stepped decode step ----
  * Rows are R = B * W hypotheses, row r = b * W + w of AST b, beam width 1 <= W <= 8; the token buffer has T columns,
  * 2 <= T <= 256 (csa_beam_supported states both limits). All fp32, deterministic (fixed reduction orders, no float
