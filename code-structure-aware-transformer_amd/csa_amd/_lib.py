@@ -183,6 +183,14 @@ class ConstrainRowsArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class LapPeArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("B", i64), ("N", i64), ("pegen_dim", i64),
+        ("adj", vp), ("num_node", vp),
+        ("pe", vp), ("eigenvalues", vp), ("status", vp), ("sweeps", vp),
+    ]
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -294,6 +302,18 @@ def lib():
     L.csa_constrain_rows_supported.argtypes = [i64]
     L.csa_constrain_rows.restype = ctypes.c_int
     L.csa_constrain_rows.argtypes = [ctypes.POINTER(ConstrainRowsArgs), vp]
+    L.csa_tree_pos_supported.restype = ctypes.c_int  # v10 additions: the structure encodings of the ablations
+    L.csa_tree_pos_supported.argtypes = [i64, i64, i64]
+    L.csa_tree_pos_bwd_workspace_bytes.restype = ctypes.c_size_t
+    L.csa_tree_pos_bwd_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    L.csa_tree_pos_fwd.restype = ctypes.c_int
+    L.csa_tree_pos_fwd.argtypes = [vp, vp, vp, i64, i64, i64, i64, f32, vp]
+    L.csa_tree_pos_bwd.restype = ctypes.c_int
+    L.csa_tree_pos_bwd.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp]
+    L.csa_lap_pe_supported.restype = ctypes.c_int
+    L.csa_lap_pe_supported.argtypes = [i64, i64]
+    L.csa_lap_pe.restype = ctypes.c_int
+    L.csa_lap_pe.argtypes = [ctypes.POINTER(LapPeArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -327,4 +347,6 @@ EXPORTED_SYMBOLS = (
     "csa_beam_supported", "csa_beam_row_topk", "csa_beam_select", "csa_decode_attn_beam",
     "csa_sample_rows_supported", "csa_sample_rows",
     "csa_constrain_rows_supported", "csa_constrain_rows",
+    "csa_tree_pos_supported", "csa_tree_pos_bwd_workspace_bytes", "csa_tree_pos_fwd", "csa_tree_pos_bwd",
+    "csa_lap_pe_supported", "csa_lap_pe",
 )

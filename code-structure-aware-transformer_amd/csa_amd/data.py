@@ -103,14 +103,83 @@ def relation_planes(parents, n_nodes, max_size, nthreads=None):
     return L, T, Lm.view(bool), Tm.view(bool)
 
 
+TREE_WIDTH, TREE_HEIGHT = 8, 16  # dataset/fast_ast_data_set.py:136-137
+TRIPLET_VOCAB = 1246  # module/csa_trans.py:141
+
+
+def tree_levels(par):
+    """(depth, sibling index) of every node of a pre-order parent array (parent[v] < v, root -1)."""
+    n = len(par)
+    depth = np.zeros(n, np.int64)
+    child_idx = np.zeros(n, np.int64)
+    nchild = np.zeros(n, np.int64)
+    for v in range(1, n):
+        p = par[v]
+        depth[v] = depth[p] + 1
+        child_idx[v] = nchild[p]
+        nchild[p] += 1
+    return depth, child_idx
+
+
+def adjacency(par, max_size):
+    """The reference's `adj` (dataset/fast_ast_data_set.py:127-128) of one tree: raw L in {-1, 0, 1} inside the
+    n x n block, so True for parent / child pairs, on the diagonal and for every unrelated pair (raw L = 0), False for
+    ancestors two or more levels apart; False outside the block. Symmetric and nearly dense."""
+    n = len(par)
+    adj = np.zeros((max_size, max_size), bool)
+    adj[:n, :n] = True
+    par = np.asarray(par, np.int64)
+    idx = np.arange(n)
+    anc = np.where(par >= 0, par[np.maximum(par, 0)], -1)  # the grandparent: distance 2
+    while True:
+        ok = anc >= 0
+        if not ok.any():
+            break
+        adj[anc[ok], idx[ok]] = False
+        adj[idx[ok], anc[ok]] = False
+        anc = np.where(ok, par[np.maximum(anc, 0)], -1)
+    return adj
+
+
+def tree_positions(par, max_size):
+    """The reference's tree_pos (dataset/fast_ast_data_set.py:84-104,136-147) of one tree, child_idx taken as the
+    sibling index: a node's vector is one_hot(min(child_idx, 7), 8) followed by its parent's (the root's is empty),
+    truncated to its last 128 entries and left-padded with zeros to 128. So the step into the node at depth d sets
+    entry 128 - 8 d + child_idx, for d <= 16. (max_size, 128) fp32, zero rows beyond the tree."""
+    n = len(par)
+    depth, child_idx = tree_levels(par)
+    W, D = TREE_WIDTH, TREE_WIDTH * TREE_HEIGHT
+    tp = np.zeros((max_size, D), np.float32)
+    for v in range(1, n):
+        tp[v] = tp[par[v]]
+        if depth[v] <= TREE_HEIGHT:
+            tp[v, D - W * depth[v] + min(child_idx[v], W - 1)] = 1.0
+    return tp
+
+
+def triplet_ids(par, max_size):
+    """Ids of the node triplets (level, parent's child_idx, child_idx) (dataset/fast_ast_data_set.py:47-50,116-122).
+    The reference looks them up in node_triplet_dictionary_*.pt, which is not available offline; this is a SYNTHETIC
+    vocabulary, the enumeration 2 + min(level, 15) * 64 + min(parent_idx, 7) * 8 + min(child_idx, 7) (< 1246), the
+    root's id that of (0, 0, 0) and PAD beyond the tree. (max_size,) int64."""
+    n = len(par)
+    depth, child_idx = tree_levels(par)
+    ids = np.full(max_size, PAD, np.int64)
+    for v in range(n):
+        pidx = child_idx[par[v]] if v > 0 else 0
+        ids[v] = 2 + min(depth[v], 15) * 64 + min(pidx, 7) * 8 + min(child_idx[v], 7)
+    return ids
+
+
 def collect_fn(batch, nthreads=None):
     """BaseASTDataSet.collect_fn (dataset/base_data_set.py:20-75) for the accelerated path: `batch` is a
     list of (item, _) with item dicts holding the preprocessed per-AST tensors -- src_seq, tgt_seq,
     target (equal lengths across the batch), raw fp32 L / T (N, N) from split_matrices.npz, num_node.
     Returns (namespace, target) like the reference's (Data, target), with the relation planes encoded
     by the native csa_collate_relations as the uint8 L, T and bool L_mask, T_mask the kernels read
-    (idx = clamp(raw + 75, 0, 149), mask = raw == 0). The ablation-only fields of the reference
-    (adj, tree_pos, triplet) are not on this path and are not collated."""
+    (idx = clamp(raw + 75, 0, 149), mask = raw == 0). The ablation fields of the reference (adj (N, N) bool,
+    tree_pos (n, 128) zero-padded to N rows as the reference pads to 150, triplet (N,)) are collated when every
+    item has all three."""
     import ctypes
     import os
     from types import SimpleNamespace
@@ -132,17 +201,25 @@ def collect_fn(batch, nthreads=None):
     data = SimpleNamespace(src_seq=stack("src_seq"), tgt_seq=stack("tgt_seq"), target=target, L=L, T=T,
                            L_mask=Lm.view(torch.bool), T_mask=Tm.view(torch.bool),
                            num_node=torch.tensor([int(it["num_node"]) for it in items]))
+    if all(k in it for it in items for k in ("adj", "tree_pos", "triplet")):
+        N = Lr.shape[1]
+        data.adj = stack("adj").to(torch.bool)
+        tps = [torch.as_tensor(it["tree_pos"], dtype=torch.float32) for it in items]
+        data.tree_pos = torch.stack([torch.cat([t, t.new_zeros(N - t.shape[0], t.shape[1])], 0) for t in tps], 0)
+        data.triplet = stack("triplet").to(torch.int64)
     return data, target
 
 
 def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None, src_vocab=10000,
-                    tgt_vocab=20000, max_tgt_len=50, native=True):
+                    tgt_vocab=20000, max_tgt_len=50, native=True, ablation_fields=False):
     """A batch of synthetic ASTs. Returns a dict of numpy arrays:
 
     L, T (B,N,N) uint8 relation indices; L_mask, T_mask (B,N,N) bool; src_mask (B,N) bool
     (True = padded node); num_node (B,); src_seq (B,N) int64 in [2, src_vocab) with PAD beyond
     num_node; tgt_seq/target (B, max_tgt_len-1) int64 (BOS ... EOS, PAD). Relation planes come from
-    the native builder (relation_planes) unless native=False."""
+    the native builder (relation_planes) unless native=False. ablation_fields=True adds what the structure-encoding
+    ablations read, built from the same trees: adj (B,N,N) bool (adjacency), tree_pos (B,N,128) fp32
+    (tree_positions) and triplet (B,N) int64 (triplet_ids, a synthetic vocabulary)."""
     rng = np.random.default_rng(seed)
     lo = max_size if min_nodes is None else min_nodes
     hi = max_size if max_nodes is None else max_nodes
@@ -176,5 +253,11 @@ def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None,
             L[b], Lm[b] = collate_relations(rl)
             T[b], Tm[b] = collate_relations(rt)
     src_mask = np.arange(max_size)[None, :] >= nn[:, None]
-    return dict(L=L, T=T, L_mask=Lm, T_mask=Tm, num_node=nn, src_seq=src, src_mask=src_mask,
-                tgt_seq=tgt[:, :-1], target=tgt[:, 1:])
+    out = dict(L=L, T=T, L_mask=Lm, T_mask=Tm, num_node=nn, src_seq=src, src_mask=src_mask,
+               tgt_seq=tgt[:, :-1], target=tgt[:, 1:])
+    if ablation_fields:
+        pars = [parents[b, :int(nn[b])].astype(np.int64) for b in range(batch)]
+        out["adj"] = np.stack([adjacency(p, max_size) for p in pars])
+        out["tree_pos"] = np.stack([tree_positions(p, max_size) for p in pars])
+        out["triplet"] = np.stack([triplet_ids(p, max_size) for p in pars])
+    return out

@@ -367,23 +367,63 @@ def make_std_mask(tgt, pad=PAD):
     return (tgt == pad).unsqueeze(-2) | future.unsqueeze(0)
 
 
+class TreePositionalEncodings(nn.Module):
+    """module/csa_trans.py:19-64 (Shiv & Quirk 2019): positions (bs, n, depth * degree) -> (bs, n, depth * degree *
+    n_feat), weighted by tanh(p)^level * sqrt((1 - tanh(p)^2) d_model / 2). The reference's name, constructor and
+    parameter `p`; on the GPU one HIP kernel per direction (pe_ops.tree_pos_encode)."""
+
+    def __init__(self, depth, degree, n_feat, d_model):
+        super().__init__()
+        self.depth = depth
+        self.width = degree
+        self.d_pos = n_feat * depth * degree
+        self.d_model = d_model
+        self.d_tree_param = self.d_pos // (self.depth * self.width)
+        self.p = nn.Parameter(torch.ones(self.d_tree_param, dtype=torch.float32), requires_grad=True)
+        self.init_weights()
+
+    def init_weights(self):
+        self.p.data.uniform_(0.7, 0.999)
+
+    def build_weights(self):
+        from .pe_ops import tree_weights
+        return tree_weights(self.p, self.depth, self.width, self.d_model)
+
+    def forward(self, positions):
+        from .pe_ops import tree_pos_encode
+        return tree_pos_encode(positions, self.p, self.depth, self.width, self.d_model)
+
+
+USE_PEGEN = ("pegen", "laplacian", "sequential", "treepos", "triplet")
+
+
 class CSATrans(nn.Module):
-    """module/csa_trans.py:67-177 (+ BaseTrans.forward/encode/decode, base_seq2seq.py:40-114)."""
+    """module/csa_trans.py:67-177 (+ BaseTrans.forward/encode/decode, base_seq2seq.py:40-114). use_pegen picks the
+    structure encoding fed to the SBM encoder: "pegen" (the CSE layers), or one of the paper's ablations, "laplacian"
+    (data.lap_pe, or the device eigenvectors of data.adj), "sequential" (sinusoidal, inside SBM), "treepos"
+    (data.tree_pos) and "triplet" (data.triplet); each has the reference's parameters and state_dict keys.
+    triplet_vocab_size is the size of the triplet embedding (the reference's 1246; its commented-out java value
+    is 1505)."""
 
     def __init__(self, src_vocab_size, tgt_vocab_size, hidden_size, num_heads, num_layers, sbm_layers, use_pegen,
                  dim_feed_forward, dropout, pe_dim, pegen_dim, sbm_enc_dim, clusters, full_att, state_dict=None,
-                 max_src_len=150, return_maps=False):
+                 max_src_len=150, return_maps=False, triplet_vocab_size=1246):
         super().__init__()
-        if use_pegen != "pegen":
-            raise NotImplementedError("only the pegen (CSE) structure encoding is on the accelerated path")
+        if use_pegen not in USE_PEGEN:
+            raise ValueError(f"use_pegen must be one of {USE_PEGEN}")
         self.num_heads = num_heads
         self.pe_dim, self.pegen_dim = pe_dim, pegen_dim
         self.use_pegen = use_pegen
         self.src_embedding = Embeddings(sbm_enc_dim - pe_dim, src_vocab_size, dropout, with_pos=False)
         self.tgt_embedding = Embeddings(hidden_size, tgt_vocab_size, dropout, with_pos=True)
-        self.src_pe_embedding = Embeddings(pegen_dim, src_vocab_size, dropout, with_pos=False)
-        self.pegen = CSE(CSE_layer(pegen_dim, num_heads, pegen_dim, dropout), num_layers, num_heads, pegen_dim,
-                         dropout=dropout, max_src_len=max_src_len)
+        if use_pegen == "pegen":
+            self.src_pe_embedding = Embeddings(pegen_dim, src_vocab_size, dropout, with_pos=False)
+            self.pegen = CSE(CSE_layer(pegen_dim, num_heads, pegen_dim, dropout), num_layers, num_heads, pegen_dim,
+                             dropout=dropout, max_src_len=max_src_len)
+        elif use_pegen == "treepos":
+            self.tree_pos_enc = TreePositionalEncodings(depth=16, degree=8, n_feat=pegen_dim // 128, d_model=pegen_dim)
+        elif use_pegen == "triplet":
+            self.triplet_emb = nn.Embedding(triplet_vocab_size, pegen_dim)
         config = {"sbm_layers": sbm_layers, "transformer_dim": sbm_enc_dim, "transformer_hidden_dim": sbm_enc_dim,
                   "head_dim": sbm_enc_dim // num_heads, "num_head": num_heads, "attn_type": "sbm",
                   "attention_grad_checkpointing": False, "attention_dropout": 0.2, "num_clusters": clusters,
@@ -408,7 +448,8 @@ class CSATrans(nn.Module):
         (GreedyGenerator runs with tgt_seq None and fills tgt_mask / tgt_emb per step)."""
         data.src_mask = data.src_seq.eq(PAD)
         data.src_emb = self.src_embedding(data.src_seq)
-        data.src_pe_emb = self.src_pe_embedding(data.src_seq)
+        if self.use_pegen == "pegen":
+            data.src_pe_emb = self.src_pe_embedding(data.src_seq)
         if getattr(data, "tgt_seq", None) is not None:
             data.tgt_mask = make_std_mask(data.tgt_seq, PAD)
             data.tgt_emb = self.tgt_embedding(data.tgt_seq)
@@ -418,9 +459,25 @@ class CSATrans(nn.Module):
         self.base_process(data)
 
     def encode(self, data):
-        """base_seq2seq.py:67-97 (pegen branch): CSE -> SBM; sparsity = mean over the SBM layers' head
-        sparsities, or 1 for the dense ablation. Returns (enc, sparsity, pe, graphs, attns)."""
-        src_pe = self.pegen(data)
+        """base_seq2seq.py:67-97: the structure encoding -> SBM; sparsity = mean over the SBM layers' head
+        sparsities, or 1 for the dense ablation. Returns (enc, sparsity, pe, graphs, attns). The laplacian mode takes
+        data.lap_pe, a precomputed (B, N, pegen_dim) tensor (what a dataset would cache), when the batch carries one,
+        and otherwise computes the eigenvectors of data.adj on the device (pe_ops.lap_pe) instead of the reference's
+        per-AST host eigh."""
+        mode = self.use_pegen
+        if mode == "pegen":
+            src_pe = self.pegen(data)
+        elif mode == "laplacian":
+            src_pe = getattr(data, "lap_pe", None)
+            if src_pe is None:
+                from .pe_ops import lap_pe
+                src_pe = lap_pe(data.adj, data.num_node, self.pegen_dim).pe
+        elif mode == "treepos":
+            src_pe = self.tree_pos_enc(data.tree_pos)
+        elif mode == "triplet":
+            src_pe = self.triplet_emb(data.triplet)
+        else:  # sequential: SBM adds its own sinusoidal encoding
+            src_pe = None
         enc, sparsity, graphs, attns, pe = self.SBM(data, src_pe, self.use_pegen)
         sparsity = 1 if sparsity[0] is None else torch.mean(torch.stack(sparsity))
         return enc, sparsity, pe, graphs, attns
@@ -1201,9 +1258,15 @@ def label_smoothing_loss(logp, target, padding_idx=PAD):
 def batch_to_device(sb, device):
     """Synthetic batch dict (csa_amd.data.synthetic_batch) -> device-resident namespace."""
     g = lambda k, dt=None: torch.as_tensor(sb[k], dtype=dt).to(device, non_blocking=True)
-    return SimpleNamespace(src_seq=g("src_seq", torch.int64), tgt_seq=g("tgt_seq", torch.int64),
+    data = SimpleNamespace(src_seq=g("src_seq", torch.int64), tgt_seq=g("tgt_seq", torch.int64),
                            L=g("L", torch.uint8), T=g("T", torch.uint8), L_mask=g("L_mask", torch.uint8),
-                           T_mask=g("T_mask", torch.uint8)), g("target", torch.int64)
+                           T_mask=g("T_mask", torch.uint8))
+    # the ablation fields (synthetic_batch(..., ablation_fields=True)), and a precomputed lap_pe, when present
+    for k, dt in (("adj", torch.uint8), ("tree_pos", torch.float32), ("triplet", torch.int64),
+                  ("num_node", torch.int32), ("lap_pe", torch.float32)):
+        if k in sb and (k != "num_node" or "adj" in sb):
+            setattr(data, k, g(k, dt))
+    return data, g("target", torch.int64)
 
 
 CONFIGS = {  # config/python.py, config/java.py, config/python_full_att.py (vocab sizes: create_vocab caps)

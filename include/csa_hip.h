@@ -460,6 +460,41 @@ typedef struct csa_constrain_rows_args {
 int csa_constrain_rows_supported(int64_t T);
 csa_status csa_constrain_rows(const csa_constrain_rows_args* a, void* stream);
 
+/* ---- v10 additions: the structure encodings of the use_pegen ablations (csrc/csa_pe.hip) ----
+ * Tree positional encoding (module/csa_trans.py:19-64): pos (rows, depth * width) fp32, p (n_feat) fp32,
+ * out / dout (rows, depth * width * n_feat) fp32, all contiguous:
+ *   out[r, j * n_feat + f] = pos[r, j] * w[j, f],  w[j, f] = tanh(p_f)^(j / width) * sqrt((1 - tanh(p_f)^2) * d_model / 2),
+ * the power an integer power by repeated multiplication (p_f = 0: w = 0 below depth 0, sqrt(d_model / 2) at depth 0).
+ * The backward writes dp (n_feat) alone, with torch's pow gradient (0 at exponent 0, 1 at exponent 1): fp64 row-block
+ * partials stored to the caller's workspace and summed in a fixed order, no atomics, bitwise repeatable.
+ * Supported: depth <= 64 and depth * width * n_feat <= 1024. */
+int csa_tree_pos_supported(int64_t depth, int64_t width, int64_t n_feat);
+size_t csa_tree_pos_bwd_workspace_bytes(int64_t rows, int64_t depth, int64_t width, int64_t n_feat);
+csa_status csa_tree_pos_fwd(const float* pos, const float* p, float* out, int64_t rows, int64_t depth, int64_t width,
+                            int64_t n_feat, float d_model, void* stream);
+csa_status csa_tree_pos_bwd(const float* pos, const float* p, const float* dout, float* dp, int64_t rows, int64_t depth,
+                            int64_t width, int64_t n_feat, float d_model, void* workspace, void* stream);
+
+/* Batched Laplacian eigenvectors (module/base_seq2seq.py:12-36,70-82), one workgroup per AST b with n = num_node[b]
+ * clamped to [0, N]: A = adj[b, :n, :n] != 0 (symmetric; anything outside the block is ignored), D = the row sums of A
+ * clipped below at 1, L = I - D^-1/2 A D^-1/2. pe[b, :n, :n] holds L's eigenvectors as columns in ascending order of
+ * eigenvalue, each with its largest-magnitude entry (the first on ties) positive, eigenvalues[b, :n] the eigenvalues;
+ * the rest of pe[b] and eigenvalues[b] is written as zeros. One-sided Jacobi on L + I in LDS; status[b] is 0, or 1 when
+ * the sweep cap was reached before convergence (nothing asserts on the device); sweeps[b] (optional) is the number of
+ * sweeps run. Deterministic, no atomics, no allocation, no sync.
+ * Supported: N <= pegen_dim and (N * (N | 1) + 2 * N + 41) * 4 bytes within the CU's 160 KiB of LDS (N <= 201). */
+typedef struct csa_lap_pe_args {
+  int64_t B, N, pegen_dim;
+  const uint8_t* adj;        /* (B, N, N) contiguous bytes, non-zero = edge */
+  const int32_t* num_node;   /* (B) */
+  float* pe;                 /* (B, N, pegen_dim) */
+  float* eigenvalues;        /* (B, N) */
+  int32_t* status;           /* (B) */
+  int32_t* sweeps;           /* (B) or NULL */
+} csa_lap_pe_args;
+int csa_lap_pe_supported(int64_t N, int64_t pegen_dim);
+csa_status csa_lap_pe(const csa_lap_pe_args* a, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);

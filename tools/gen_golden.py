@@ -7,9 +7,10 @@ re-verifies that this is bit-identical to the real CPU draw), runs forward + bac
 seeded inputs, and writes small ``.npz`` fixtures to tests/golden/. The reference never
 travels to the GPU box; only these fixtures do.
 
-Run:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [large | dims | mapgrad | ast]
+Run:  PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [large | dims | mapgrad | ast | pe]
       (`large` = only the production-shape fixtures: rel_attn_n150_dk64, greedy_tiny, csatrans_java;
-       `dims` = csatrans_java + csatrans_python with their fp64 error budgets)
+       `dims` = csatrans_java + csatrans_python with their fp64 error budgets;
+       `pe` = the structure-encoding ablations: csatrans_tiny_{seq,treepos,triplet,lap} and tree_pos_ref)
 """
 import importlib.util
 import math
@@ -393,6 +394,134 @@ def csatrans_case(name, seed):
     print(f"{name}: loss={loss.item():.5f} sparsity={sparsity.item():.5f} keys={len(model.state_dict())}")
 
 
+PE_MODES = {  # fixture -> (use_pegen, what differs from csatrans_case's dims)
+    "csatrans_tiny_seq": ("sequential", dict(pe_dim=0)),
+    "csatrans_tiny_treepos": ("treepos", dict(pegen_dim=256)),  # n_feat = 2
+    "csatrans_tiny_triplet": ("triplet", {}),
+    "csatrans_tiny_lap": ("laplacian", {}),
+}
+PE_GRAD_KEYS = GRAD_KEYS + ("tree_pos_enc.p", "triplet_emb.weight")
+
+
+def reference_tree_positions(par):
+    """The reference's FastASTDataSet.gen_tree_positions (dataset/fast_ast_data_set.py:84-104) on one pre-order
+    parent array, child_idx = the sibling index, followed by convert_ast_to_edges' cut to the last 128 entries and
+    left zero padding (:136-147). (n, 128) fp32."""
+    load_full_reference_package()
+    s = importlib.util.spec_from_file_location("dataset.fast_ast_data_set", f"{REF}/dataset/fast_ast_data_set.py")
+    m = importlib.util.module_from_spec(s)
+    s.loader.exec_module(m)
+    from csa_amd.data import tree_levels
+    depth, child_idx = tree_levels(par)
+    nodes = [types.SimpleNamespace(num=v, level=int(depth[v]), child_idx=int(child_idx[v]), parent=None)
+             for v in range(len(par))]
+    for v in range(1, len(par)):
+        nodes[v].parent = nodes[par[v]]
+    width, height = 8, 16
+    pos = m.FastASTDataSet.gen_tree_positions(None, nodes, width, height)
+    rows = []
+    for v in pos.values():
+        v = v[-width * height:] if len(v) > width * height else v
+        rows.append(torch.cat([torch.zeros(width * height - len(v)), v]))
+    return torch.stack(rows).numpy().astype(np.float32)
+
+
+def tree_pos_case(name, seed):
+    """tree_pos of synthetic trees by the reference's own generator: the sizes of csatrans_case's batch and a deep
+    chain-like tree whose depth passes 16 (the cut to the last 128 entries)."""
+    from csa_amd.data import random_tree
+    rng = np.random.default_rng(seed)
+    pars = [random_tree(n, rng)[0] for n in (1, 2, 20, 150)]
+    pars.append(random_tree(60, rng, max_children=1)[0])                   # a chain: depth 59
+    pars.append(random_tree(150, np.random.default_rng(seed + 1), max_children=2)[0])
+    res = {}
+    for i, par in enumerate(pars):
+        res[f"par{i}"] = np.asarray(par, np.int64)
+        res[f"tree_pos{i}"] = reference_tree_positions(par)
+    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **res)
+    print(f"{name}: {len(pars)} trees, max depth rows {[int(res[f'tree_pos{i}'].sum(1).max()) for i in range(len(pars))]}")
+
+
+def csatrans_pe_mode_case(name, seed):
+    """csatrans_case for one of the structure-encoding ablations (use_pegen = sequential / treepos / triplet /
+    laplacian): B = 2, N = 20, the same deterministic fill, host-supplied uniforms moved off fp32 ties by the
+    java-dims rule (no draw within TIE_MARGIN of its probability; asserted). The laplacian case also keeps the
+    reference's adj, eigenvectors and eigenvalues; its encode() names the device literally, which is shimmed."""
+    mode, over = PE_MODES[name]
+    refmod, Data = load_full_reference_package()
+    import module.base_seq2seq as bs
+    s = importlib.util.spec_from_file_location("ref_label_smooth", f"{REF}/utils/label_smooth.py")
+    ls = importlib.util.module_from_spec(s)
+    s.loader.exec_module(ls)
+    torch.manual_seed(seed)
+    kw = dict(src_vocab_size=50, tgt_vocab_size=60, hidden_size=64, num_heads=8, num_layers=1, sbm_layers=2,
+              use_pegen=mode, dim_feed_forward=128, dropout=0.2, pe_dim=32, pegen_dim=128, sbm_enc_dim=512,
+              clusters=[10, 12], full_att=False)
+    kw.update(over)
+    model = refmod.CSATrans(**kw).eval()
+    fill_params_deterministic(model, seed)
+    B, N = 2, 20
+    sb = synthetic_batch(B, max_size=N, seed=seed, min_nodes=12, max_nodes=N, src_vocab=50, tgt_vocab=60,
+                         max_tgt_len=9, ablation_fields=True)
+    f = lambda a: torch.from_numpy(np.asarray(a))
+    data = Data(src_seq=f(sb["src_seq"]), tgt_seq=f(sb["tgt_seq"]), adj=f(sb["adj"]), tree_pos=f(sb["tree_pos"]),
+                triplet=f(sb["triplet"]), num_node=f(sb["num_node"]))
+    g = torch.Generator().manual_seed(seed + 1)
+    us = [torch.rand(B, 8, N, N, generator=g).numpy() for _ in range(2)]
+    used, margins = [], []
+
+    def bern(p):
+        u, _, _ = gi.nudge_uniforms(us[len(used)], p.detach().numpy())
+        used.append(u)
+        margins.append(float(np.abs(u - p.detach().numpy()).min()))
+        return (torch.from_numpy(u) < p).to(p.dtype)
+
+    eig = []
+    real_lap_eig, real_to = bs.lap_eig, torch.Tensor.to
+
+    def lap_eig(adj, n, deg):
+        vec, val = real_lap_eig(adj, n, deg)
+        eig.append((vec, val))
+        return vec, val
+
+    torch.bernoulli = bern
+    bs.lap_eig = lap_eig
+    torch.Tensor.to = lambda self, *a, **k: real_to(self, *("cpu" if isinstance(x, str) and x == "cuda" else x
+                                                               for x in a), **k)
+    try:
+        out, sparsity, src_pe, graphs, attns = model(data)
+    finally:
+        torch.bernoulli = _real_bernoulli
+        bs.lap_eig = real_lap_eig
+        torch.Tensor.to = real_to
+    assert len(used) == 2 and min(margins) >= gi.TIE_MARGIN * (1 - 1e-3), margins
+    loss = ls.LabelSmoothing(padding_idx=0, smoothing=0.0)(out, f(sb["target"]))
+    (loss + 1e-2 * sparsity).backward()
+    res = {"src_seq": sb["src_seq"], "tgt_seq": sb["tgt_seq"], "target": sb["target"], "num_node": sb["num_node"],
+           "u0": used[0], "u1": used[1], "out": np32(out), "sparsity": np.array([sparsity.item()], np.float32),
+           "loss": np.array([loss.item()], np.float32)}
+    if mode == "treepos":
+        res["tree_pos"] = sb["tree_pos"]
+        res["p:tree_pos_enc.p"] = np32(model.tree_pos_enc.p)  # what the deterministic fill leaves in the parameter
+    if mode == "triplet":
+        res["triplet"] = sb["triplet"]
+    if mode == "laplacian":
+        assert len(eig) == B
+        vec = np.zeros((B, N, kw["pegen_dim"]), np.float32)
+        val = np.zeros((B, N), np.float32)
+        for b, (v, w) in enumerate(eig):
+            n = v.shape[0]
+            vec[b, :n, :n], val[b, :n] = v.numpy(), w.numpy()
+        res.update(adj=sb["adj"], lap_vec=vec, lap_val=val)
+    res["state_keys"] = np.array(sorted(model.state_dict().keys()))
+    for k, p in model.named_parameters():
+        if any(t in k for t in PE_GRAD_KEYS):
+            res["g:" + k] = np32(p.grad)
+    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **res)
+    print(f"{name}: loss={loss.item():.5f} sparsity={sparsity.item():.5f} keys={len(model.state_dict())} "
+          f"grads={sum(k.startswith('g:') for k in res)} tie margin={min(margins):.2e}")
+
+
 def rel_attn_large_case(name, B, N, dk, L, seed):
     """rel_attn at the production head size (d_k = pegen_dim/8 = 64, N = L = 150). Inputs are
     regenerated from PCG64 (tests/golden_inputs.py:rel_inputs), so only relations and outputs are stored."""
@@ -600,6 +729,11 @@ def main():
     if sys.argv[1:] == ["ast"]:
         ast_relations_case("ast_relations", seed=91)
         return
+    if sys.argv[1:] == ["pe"]:  # only the structure-encoding ablation fixtures
+        for i, name in enumerate(PE_MODES):
+            csatrans_pe_mode_case(name, seed=73 + i)
+        tree_pos_case("tree_pos_ref", seed=92)
+        return
     if sys.argv[1:] == ["mapgrad"]:  # only the round-2 map-gradient fixtures
         sbm_case("sbm_n37_mapgrad", B=2, H=2, N=37, d=64, k=10, pad_counts=[0, 7], seed=17, map_grads=True)
         sbm_case("sbm_n33_d96_mapgrad", B=1, H=2, N=33, d=96, k=10, pad_counts=[1], seed=18, map_grads=True)
@@ -635,6 +769,9 @@ def main():
     generator_case("generator_v1003", seed=64)
     adamw_case("adamw_nobias", seed=62)
     csatrans_case("csatrans_tiny", seed=71)
+    for i, name in enumerate(PE_MODES):
+        csatrans_pe_mode_case(name, seed=73 + i)
+    tree_pos_case("tree_pos_ref", seed=92)
     if True:
         sbm_case("sbm_n37_mapgrad", B=2, H=2, N=37, d=64, k=10, pad_counts=[0, 7], seed=17, map_grads=True)
         sbm_case("sbm_n33_d96_mapgrad", B=1, H=2, N=33, d=96, k=10, pad_counts=[1], seed=18, map_grads=True)
