@@ -342,7 +342,7 @@ class _ResidualDropoutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         bm, p, seed = ctx.cfg
-        g = (gy.transpose(0, 1) if bm else gy).contiguous()  # same memory order as the forward
+        g = _kernel_operand(gy.transpose(0, 1) if bm else gy)  # same memory order as the forward
         d_o = torch.empty_like(g)
         p_ = lambda t: ctypes.c_void_p(t.data_ptr())
         with on_device(g.device):
@@ -354,6 +354,14 @@ class _ResidualDropoutFn(torch.autograd.Function):
 
 def _aligned(t):
     return t.data_ptr() % 16 == 0
+
+
+def _kernel_operand(t):
+    """t as a contiguous, 16-byte aligned tensor (what the dropout kernels' dwordx4 loads need): t itself
+    when it already is one, else a copy. An upstream gradient may be a contiguous view that starts
+    anywhere inside an allocation; a fresh allocation is aligned."""
+    t = t.contiguous()
+    return t if _aligned(t) else t.clone()
 
 
 def residual_dropout(x, o, dropout: nn.Dropout):
@@ -389,7 +397,7 @@ class _GeluDropoutFn(torch.autograd.Function):
     def backward(ctx, gy):
         (hm,) = ctx.saved_tensors
         bm, p, seed = ctx.cfg
-        g = (gy.transpose(0, 1) if bm else gy).contiguous()
+        g = _kernel_operand(gy.transpose(0, 1) if bm else gy)
         dh = torch.empty_like(hm)
         p_ = lambda t: ctypes.c_void_p(t.data_ptr())
         with on_device(g.device):

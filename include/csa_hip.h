@@ -517,7 +517,10 @@ csa_status csa_layernorm_bwd(const float* dy, const float* x, const float* stats
  * `self.mlpblock(self.norm2(X)) + X`, whose last mlpblock module is the Dropout) ----
  * x, o, y, dy, d_o: n fp32 elements in the same memory order, 16-byte aligned; 0 < p < 1.
  * y = x + keep * o / (1 - p); d_o = keep * dy / (1 - p) (the residual gradient is dy itself).
- * keep for element i: Philox4x32-7 stream 5 (oracle/philox.py:res_keep), regenerated by the backward. */
+ * keep for element i: Philox4x32-7 stream 5 (oracle/philox.py:res_keep), regenerated by the backward.
+ * All 64 bits of `seed` are the Philox key (low word, high word); the low 32 bits of `offset` enter the
+ * last counter word as (5 << 28) ^ (uint32_t)offset, its high 32 bits are ignored
+ * (tests/test_elementwise_train_gpu.py: distinct (seed, offset) pairs give distinct masks). */
 csa_status csa_residual_dropout_fwd(const float* x, const float* o, float* y, int64_t n, float p, uint64_t seed,
                                     uint64_t offset, void* stream);
 csa_status csa_residual_dropout_bwd(const float* dy, float* d_o, int64_t n, float p, uint64_t seed, uint64_t offset,
@@ -527,7 +530,10 @@ csa_status csa_residual_dropout_bwd(const float* dy, float* d_o, int64_t n, floa
  * `linear2(dropout(gelu(linear1(x))))`; module/sbm_model.py:22-26 mlpblock GELU -> Dropout) ----
  * h, y, dy, dh: n fp32 elements in the same memory order, 16-byte aligned; 0 <= p < 1.
  * y = keep * gelu(h) / (1 - p) (exact erf GELU); dh = keep * dy / (1 - p) * gelu'(h).
- * keep for element i: Philox4x32-7 stream 6 (oracle/philox.py:ffn_keep), regenerated by the backward. */
+ * keep for element i: Philox4x32-7 stream 6 (oracle/philox.py:ffn_keep), regenerated by the backward.
+ * Key and counter as above: all 64 bits of `seed`, (6 << 28) ^ (uint32_t)offset; p = 0 reads neither.
+ * Non-finite h gives the IEEE value of these formulas: gelu(+inf) = +inf, gelu(-inf) = NaN, gelu'(+-inf) = NaN,
+ * NaN stays NaN; a dropped element is 0 * value, so a dropped +inf is NaN as well. */
 csa_status csa_gelu_dropout_fwd(const float* h, float* y, int64_t n, float p, uint64_t seed, uint64_t offset,
                                 void* stream);
 csa_status csa_gelu_dropout_bwd(const float* dy, const float* h, float* dh, int64_t n, float p, uint64_t seed,
