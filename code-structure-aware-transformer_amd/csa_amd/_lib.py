@@ -191,6 +191,18 @@ class LapPeArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class CsaSeqMetricsArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("hyp", vp), ("rows", i64), ("Th", i64), ("hyp_stride", i64),
+        ("ref", vp), ("Tr", i64), ("ref_stride", i64),
+        ("group", i64), ("eos_id", i64),
+        ("stats", vp), ("bleu", vp), ("rouge", vp),
+    ]
+
+
+SEQ_METRICS_FIELDS = 12  # CSA_SEQ_METRICS_FIELDS: m1..m4, poss1..poss4, len_h, len_r, lcs, valid
+
+
 class CsaError(RuntimeError):
     pass
 
@@ -314,6 +326,10 @@ def lib():
     L.csa_lap_pe_supported.argtypes = [i64, i64]
     L.csa_lap_pe.restype = ctypes.c_int
     L.csa_lap_pe.argtypes = [ctypes.POINTER(LapPeArgs), vp]
+    L.csa_seq_metrics_supported.restype = ctypes.c_int  # v10 addition: validation metrics of decoded ids
+    L.csa_seq_metrics_supported.argtypes = [i64, i64]
+    L.csa_seq_metrics.restype = ctypes.c_int
+    L.csa_seq_metrics.argtypes = [ctypes.POINTER(CsaSeqMetricsArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -349,4 +365,5 @@ EXPORTED_SYMBOLS = (
     "csa_constrain_rows_supported", "csa_constrain_rows",
     "csa_tree_pos_supported", "csa_tree_pos_bwd_workspace_bytes", "csa_tree_pos_fwd", "csa_tree_pos_bwd",
     "csa_lap_pe_supported", "csa_lap_pe",
+    "csa_seq_metrics_supported", "csa_seq_metrics",
 )

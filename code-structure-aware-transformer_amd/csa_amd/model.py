@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from .data import BOS, EOS, UNK
 from .glue import LayerNorm, Linear, MultiheadAttention, gelu_dropout, residual_dropout
+from .metrics import SummaryMetrics, evaluate  # noqa: F401 (the scorer of what the generators below return)
 from .module.disentangled_attn import DisentangledAttn
 from .module.sbm_attn import Attention
 

@@ -460,6 +460,30 @@ typedef struct csa_constrain_rows_args {
 int csa_constrain_rows_supported(int64_t T);
 csa_status csa_constrain_rows(const csa_constrain_rows_args* a, void* stream);
 
+/* ---- v10 additions: validation metrics of decoded ids (csrc/csa_metric.hip) ----
+ * Smoothed sentence BLEU-4 (valid_metrices/google_bleu.py compute_bleu(smooth=True) behind bleu_output_transform) and
+ * ROUGE-L (valid_metrices/rouge/rouge.py calc_score, beta = 1.2) of `rows` hypothesis rows against rows / group
+ * reference rows; hypothesis row r belongs to reference r / group (1: greedy, W: a beam's n-best list, S: samples).
+ * A row's length is the index of its first eos_id, or its full width when it holds none; PAD, UNK and every other id
+ * are ordinary tokens. An empty hypothesis is the reference's one-token placeholder, which matches nothing: len_h = 1,
+ * poss = (1, 0, 0, 0), no match, lcs = 0. A row whose reference is empty is invalid: valid = 0 and every other output 0.
+ * Per row, n = 1..4: m_n = sum over n-grams g of min(count_hyp(g), count_ref(g)), poss_n = max(len_h - n + 1, 0),
+ *   bleu  = exp(sum_n 0.25 * log((m_n + 1) / (poss_n + 1))) * bp, bp = 1 if len_h / len_r > 1 else exp(1 - len_r / len_h);
+ *   rouge = (1 + beta^2) p r / (r + beta^2 p), p = lcs / len_h, r = lcs / len_r; 0 when lcs = 0;
+ * both in fp64 on the device. stats row: m1..m4, poss1..poss4, len_h, len_r, lcs, valid (CSA_SEQ_METRICS_FIELDS int32).
+ * 1 <= Th, Tr <= 256 (csa_seq_metrics_supported). A row's outputs depend on that row and its reference alone.
+ * Deterministic, no atomics, no allocation, no sync: capturable. */
+#define CSA_SEQ_METRICS_FIELDS 12
+typedef struct csa_seq_metrics_args {
+  const int64_t* hyp; int64_t rows, Th, hyp_stride;   /* (rows, Th) ids, row stride >= Th */
+  const int64_t* ref; int64_t Tr, ref_stride;         /* (rows / group, Tr) ids, row stride >= Tr */
+  int64_t group, eos_id;                              /* group >= 1 and divides rows */
+  int32_t* stats;                                     /* (rows, 12) contiguous */
+  double* bleu; double* rouge;                        /* (rows) each */
+} csa_seq_metrics_args;
+int csa_seq_metrics_supported(int64_t Th, int64_t Tr);
+csa_status csa_seq_metrics(const csa_seq_metrics_args* a, void* stream);
+
 /* ---- v10 additions: the structure encodings of the use_pegen ablations (csrc/csa_pe.hip) ----
  * Tree positional encoding (module/csa_trans.py:19-64): pos (rows, depth * width) fp32, p (n_feat) fp32,
  * out / dout (rows, depth * width * n_feat) fp32, all contiguous:
