@@ -14,18 +14,19 @@ reference's and reference checkpoints load. What changes:
   MultiheadAttention keep nn's parameters and state_dict keys; they run the decoder's permuted
   sequence-first views on their batch-first memory instead of copying them. Embeddings, dropout,
   GELU and SDPA are stock PyTorch-ROCm, as in the reference.
+
+What has no counterpart in the reference lives elsewhere and is re-exported here: the KV-cached decoding strategies in
+csa_amd.decoding (over Embeddings.step, BaseDecoder.step and DecodeCache below), the metrics in csa_amd.metrics.
 """
 import copy
 import math
-from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .data import BOS, EOS, UNK
+from .data import BOS, UNK
 from .glue import LayerNorm, Linear, MultiheadAttention, gelu_dropout, residual_dropout
 from .metrics import SummaryMetrics, evaluate  # noqa: F401 (the scorer of what the generators below return)
 from .module.disentangled_attn import DisentangledAttn
@@ -525,662 +526,17 @@ class GreedyGenerator(nn.Module):
         return ys[:, 1:]
 
 
-@dataclass(frozen=True)
-class DecodingConstraints:
-    """Which tokens a decoding step may choose, for CachedGreedyGenerator, BeamSearchGenerator and SamplingGenerator
-    (decode_ops.constrain_rows, csrc/csa_constrain.hip): a frozen, hashable value.
-
-    repetition_penalty theta > 0 (1: off): the logit z of every token already in the row's history, BOS included,
-    becomes z / theta if z > 0 else z * theta, once however often the token occurs. no_repeat_ngram_size n >= 0 (0: off):
-    a token that would complete an n-gram the history already holds is banned. min_length: eos_id is banned at the
-    steps t < min_length, so an output holds at least min_length tokens before its EOS (off at 0 or with eos_id None).
-    suppress_ids: at most 256 ids banned at every step. A banned token is a -inf logit to the selection that follows,
-    which renormalises over what is left. `active` is False when every rule is off; the generators then run exactly
-    the launches they run without constraints."""
-
-    repetition_penalty: float = 1.0
-    no_repeat_ngram_size: int = 0
-    min_length: int = 0
-    suppress_ids: tuple = ()
-    eos_id: Optional[int] = EOS
-
-    MAX_SUPPRESS = 256
-
-    def __post_init__(self):
-        theta = float(self.repetition_penalty)
-        if not 0.0 < theta < float("inf"):
-            raise ValueError("DecodingConstraints: repetition_penalty must be positive and finite (1 turns it off)")
-        for name in ("no_repeat_ngram_size", "min_length"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or int(v) != v or v < 0:
-                raise ValueError(f"DecodingConstraints: {name} must be a non-negative integer (0 turns it off)")
-        ids, eos = tuple(self.suppress_ids), self.eos_id
-        if len(ids) > self.MAX_SUPPRESS or any(isinstance(i, bool) or int(i) != i or not 0 <= i < 2 ** 31 for i in ids):
-            raise ValueError("DecodingConstraints: suppress_ids holds at most 256 non-negative integer ids")
-        if eos is not None and (isinstance(eos, bool) or int(eos) != eos or eos < 0):
-            raise ValueError("DecodingConstraints: eos_id must be a non-negative integer or None")
-        for name, v in (("repetition_penalty", theta), ("no_repeat_ngram_size", int(self.no_repeat_ngram_size)),
-                        ("min_length", int(self.min_length)), ("suppress_ids", tuple(int(i) for i in ids)),
-                        ("eos_id", None if eos is None else int(eos))):
-            object.__setattr__(self, name, v)  # the normalised value (frozen: no plain assignment)
-
-    @property
-    def active(self):
-        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or bool(self.suppress_ids)
-                or (self.min_length > 0 and self.eos_id is not None))
-
-    def apply(self, logits, ys, t, fin=None, suppress=None):
-        """One constrain_rows call with this value's rules; suppress: suppress_tensor(device) made once."""
-        from .decode_ops import constrain_rows
-        return constrain_rows(logits, ys, t, fin=fin, repetition_penalty=self.repetition_penalty,
-                              no_repeat_ngram=self.no_repeat_ngram_size, min_length=self.min_length, eos_id=self.eos_id,
-                              suppress=suppress)
-
-    def suppress_tensor(self, device):
-        """The suppress list as the static int32 device tensor that the kernel reads, or None for an empty list."""
-        return torch.tensor(self.suppress_ids, dtype=torch.int32, device=device) if self.suppress_ids else None
-
-
-class _SteppedDecoding:
-    """graph=True of CachedGreedyGenerator and BeamSearchGenerator: the device-stepped decode step (every kernel reads
-    the step from the 4-byte device counter e.t_dev, so every step issues the same launches), captured once per
-    (device, B, S, max_tgt_len, the generator's key extras, parameter addresses) as one single-stream
-    torch.cuda.CUDAGraph over static buffers and replayed max_tgt_len - 1 times per call. `captures` counts the graphs
-    captured. The generator supplies _state(cache, **kw), _reset(e), _device_step(e) and, if it must, _check_capture.
-
-    constraints= (a DecodingConstraints) is shared by the three generators: when active, one decode_ops.constrain_rows
-    call sits between generator.linear and the selection of every step, the value joins the graph key extras and the
-    suppress list is a static device tensor of the state; None or an inactive value changes nothing.
-
-    early_stop=True (needs an eos_id, so a finished flag e.fin per row) is one rule for the three generators: decoding
-    stops after the first step that BEGAN with every row finished, one step after the step s that finished the last
-    row, so steps 0..s+1 run; without such a step all max_tgt_len - 1 run. The extra step is the one after which the
-    state is a fixed point (for the beam, the step in which the selection orders the all-finished hypotheses by cum), so
-    ids, scores and log-probabilities are bitwise those of the full run; columns never written stay PAD / 0 as _reset
-    leaves them. On the device the rule is a latch: the step ends with decode_ops.decode_advance in place of the
-    counter's increment, which counts the step in the state words e.stop = {all_prev, steps_run, parked, 0} and parks
-    the counter at -1; every step kernel returns on a negative counter, so a surplus replay stores nothing. The host
-    (_run_steps) issues replays in chunks of poll_every, copies the state words to a pinned buffer after each chunk
-    (outside the graph, same stream, non-blocking) and, before issuing chunk k + 2, waits for chunk k's copy and stops
-    if it reports parked: at most two chunks are ever in flight and no kernel waits on the host. last_steps_run is the
-    latch's count after the call (max_tgt_len - 1 without early_stop), exact whatever the chunking; last_replays is
-    the number of steps issued, at most last_steps_run + 2 * poll_every. False keeps the launches, the graph key and
-    the captured graph of a generator built without the keyword."""
-
-    MAX_GRAPHS = 4  # captured (shape, weights) entries kept per generator; the oldest is evicted
-    POLL_EVERY = 2  # replays per chunk of an early-stopping graph=True call: the fastest of 2, 4 and 8
-                    # (tools/bench_early_stop.py, profiles/early_stop_decode.json)
-
-    def _init_stepped(self, graph, early_stop=False, **cache_options):
-        self.graph = graph
-        self.captures = 0      # graphs captured so far (graph=True on a CUDA model; 0 otherwise)
-        self._graphs = {}      # key -> SimpleNamespace of static buffers and the captured step (insertion-ordered)
-        self._keep_graph = False  # keep the captured hipGraph_t (tools/bench_greedy.py counts its nodes)
-        self._cache_options = cache_options  # what the generator asks of BaseDecoder.empty_cache
-        self.early_stop = bool(early_stop)
-        self.poll_every = self.POLL_EVERY
-        self.last_steps_run = None  # decode steps that ran in the last call
-        self.last_replays = None    # decode steps issued in the last call (>= last_steps_run: parked ones store nothing)
-        self._check_early_stop()
-
-    def _check_early_stop(self):
-        if self.early_stop and self.eos_id is None:
-            raise ValueError(f"{type(self).__name__}: early_stop=True needs an eos_id (without one no row ever finishes)")
-
-    def _stop_key(self):
-        """What early_stop adds to the graph key extras: nothing when it is off."""
-        return ("early_stop",) if self.early_stop else ()
-
-    def _stop_state(self, device):
-        """The latch's state words {all_prev, steps_run, parked, reserved} of a step's state (None without early_stop)."""
-        return torch.zeros(4, dtype=torch.int32, device=device) if self.early_stop else None
-
-    def _advance(self, e):
-        """The end of a device step, after the counter's last reader: the increment, or the early-stop latch."""
-        if e.stop is None:
-            e.t_dev.add_(1)
-        else:
-            from .decode_ops import decode_advance
-            decode_advance(e.fin, e.t_dev, e.stop, self.max_tgt_len)
-
-    def _run_steps(self, e, graphed, after_step=None):
-        """The decode steps of one call on the reset state e: replays of e.graph (graphed) or eager _device_step calls,
-        max_tgt_len - 1 of them or, with early_stop, until the latch reports parked (see the class docstring).
-        after_step() runs on the host after each issued step. Sets last_steps_run and last_replays."""
-        self._check_early_stop()
-        n = self.max_tgt_len - 1
-        step = e.graph.replay if graphed else (lambda: self._device_step(e))
-        if e.stop is None:
-            for _ in range(n):
-                step()
-                if after_step is not None:
-                    after_step()
-            self.last_steps_run = self.last_replays = n
-            return
-        issued = 0
-        if not graphed:  # host-bound already: read the latch after every step
-            while issued < n:
-                step()
-                issued += 1
-                if after_step is not None:
-                    after_step()
-                if int(e.stop[2]) != 0:
-                    break
-            self.last_steps_run, self.last_replays = int(e.stop[1]), issued
-            return
-        poll = max(1, int(self.poll_every))
-        chunks = (n + poll - 1) // poll
-        if e.stop_host is None or e.stop_host.shape[0] < chunks + 1:
-            e.stop_host = torch.empty(chunks + 1, 4, dtype=torch.int32, pin_memory=True)
-        stream = torch.cuda.current_stream(e.stop.device)
-        events = []
-        while issued < n:
-            k = len(events)
-            if k >= 2:  # chunks k - 1 and k - 2 are in flight: wait for the older one's state words
-                events[k - 2].synchronize()
-                if int(e.stop_host[k - 2, 2]) != 0:
-                    break
-            for _ in range(min(poll, n - issued)):
-                step()
-                issued += 1
-                if after_step is not None:
-                    after_step()
-            e.stop_host[k].copy_(e.stop, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            events.append(ev)
-        e.stop_host[chunks].copy_(e.stop, non_blocking=True)
-        stream.synchronize()
-        self.last_steps_run, self.last_replays = int(e.stop_host[chunks, 1]), issued
-
-    @property
-    def constraints(self):
-        """The active DecodingConstraints, or None. Assignable between calls: None and an inactive value are the same
-        thing, no constraint step at all (the launches, the graph key and the captured graph of a generator built
-        without the keyword); another active value gets a captured graph of its own."""
-        return self._constraints
-
-    @constraints.setter
-    def constraints(self, constraints):
-        if constraints is not None and not isinstance(constraints, DecodingConstraints):
-            raise TypeError("constraints must be a DecodingConstraints or None")
-        object.__setattr__(self, "_constraints", constraints if constraints is not None and constraints.active else None)
-
-    def _suppress_state(self, device):
-        """The suppress list as the static device tensor of a step's state (None without one)."""
-        return None if self.constraints is None else self.constraints.suppress_tensor(device)
-
-    def _constraint_key(self):
-        """What the constraints add to the graph key extras: nothing when there are none."""
-        return () if self.constraints is None else (self.constraints,)
-
-    def _check_constraints_capture(self, enc):
-        from ._lib import lib
-        if self.constraints is not None and (not lib().csa_constrain_rows_supported(self.max_tgt_len)
-                                             or enc.dtype != torch.float32):
-            raise ValueError(f"{type(self).__name__}: graph=True with constraints needs fp32 and max_tgt_len <= 1024 "
-                             "(csa_constrain_rows_supported)")
-
-    def _step_params(self):
-        m = self.model
-        mods = (m.tgt_embedding, m.decoder, m.generator.linear)
-        return [p for mod in mods for p in list(mod.parameters()) + list(mod.buffers())]
-
-    def _check_capture(self, enc):
-        """Raises where the generator's step cannot be captured for this memory."""
-        self._check_constraints_capture(enc)
-
-    def _capture(self, enc, **state_kw):
-        self._check_capture(enc)
-        dev = enc.device
-        cache = self.model.decoder.empty_cache(enc.size(0), self.max_tgt_len, dev, enc.dtype, S=enc.size(1),
-                                               **self._cache_options)
-        e = self._state(cache, **state_kw)
-        self._reset(e)
-        # one eager device-stepped step on a side stream first: code objects, hipBLASLt heuristics and workspaces
-        # are then in place and stay outside the capture
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._device_step(e)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        e.graph = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
-        with torch.cuda.graph(e.graph):  # a single capture stream: the captured step has no parallel branches
-            self._device_step(e)
-        if self._keep_graph:
-            e.graph.instantiate()
-        self.captures += 1
-        return e
-
-    def _graph_entry(self, enc, src_mask, key_extra, **state_kw):
-        """The captured entry for this memory (captured now if there is none, the oldest evicted), its static memory
-        buffers loaded from enc and src_mask and its state reset to step 0: ready for max_tgt_len - 1 replays."""
-        B, S, T = enc.size(0), enc.size(1), self.max_tgt_len
-        # reallocated parameters recapture; weights updated in place are simply read by the next replay
-        key = (enc.device, B, S, T, *key_extra, tuple(p.data_ptr() for p in self._step_params()))
-        e = self._graphs.get(key)
-        if e is None:
-            with torch.cuda.device(enc.device):
-                e = self._capture(enc, **state_kw)
-            while len(self._graphs) >= self.MAX_GRAPHS:
-                del self._graphs[next(iter(self._graphs))]
-            self._graphs[key] = e
-        self.model.decoder.load_memory(e.cache, enc, src_mask)
-        self._reset(e)
-        return e
-
-
-class CachedGreedyGenerator(_SteppedDecoding, GreedyGenerator):
-    """GreedyGenerator with a key/value cache: the same tokens from one decoder pass per NEW position.
-
-    The decoder is causal and the key-padding mask of positions <= j never changes as ys grows, so step t needs only
-    position t: its embedding, BaseDecoder.step against the cached self-attention keys / values and the once-projected
-    encoder memory (csa_decode_attn), the Generator's linear on the B last rows, and the row argmax written into
-    ys[:, t+1] with the next step's PAD byte (csa_argmax_rows). Eval-mode log(softmax(z)) is monotone in z, so the
-    argmax of the logits is the reference's torch.max(out, 1)[1] and the softmax is skipped unless return_logp asks for
-    the (max_tgt_len-1, B, V) last-position log-probabilities. All max_tgt_len-1 steps run, as in the reference, unless
-    early_stop asks otherwise (below). In training mode this defers to GreedyGenerator.
-
-    graph=True (eval mode, CUDA model): the loop above is bound by the host, about 70 small launches per step issued
-    from Python. The step is instead run device-stepped (csa_decode_embed, csa_decode_attn_step, csa_argmax_rows_step)
-    and replayed from one captured graph per (..., return_logp, ...) (_SteppedDecoding); process_data, encode (its
-    Philox key comes from the CPU generator) and the memory projections stay eager. Same ids and log-probabilities,
-    bitwise.
-
-    constraints=DecodingConstraints(...): the logits of every step go through decode_ops.constrain_rows before the
-    argmax (history = the row's tokens so far, BOS included; there is no finished flag here, so the rules keep applying
-    after an EOS), and return_logp reports the constrained distribution. Training mode with active constraints
-    raises: the uncached loop it defers to has no such step.
-
-    eos_id (default None: the behaviour above, bit for bit): the generator keeps a finished flag per row, fin (B,) uint8.
-    A row that has emitted eos_id takes PAD from then on (csa_argmax_rows_fin_step) and active constraints leave it
-    alone. With the head-repeated PAD mask a finished row's PAD columns enter other rows' masks, so this is a behaviour
-    of its own, not a truncation of the ids without eos_id. early_stop=True (needs eos_id; _SteppedDecoding) stops the
-    call once every row has finished, with the ids of the full run, and return_logp then returns the steps that ran,
-    (last_steps_run, B, V). Training mode with an eos_id raises."""
-
-    def __init__(self, model, max_tgt_len, multi_gpu=False, graph=False, constraints=None, eos_id=None,
-                 early_stop=False):
-        super().__init__(model, max_tgt_len, multi_gpu)
-        self.eos_id = eos_id
-        self._init_stepped(graph, early_stop, repeat_heads=True)  # as CSATrans.decode masks
-        self.constraints = constraints
-
-    def forward(self, data, return_logp=False):
-        m = self.model
-        if m.training:
-            if self.constraints is not None or self.eos_id is not None:
-                raise RuntimeError("CachedGreedyGenerator: constraints and eos_id are for inference only (the uncached "
-                                   "loop that training mode defers to has neither)")
-            ys = super().forward(data)
-            self.last_steps_run = self.last_replays = self.max_tgt_len - 1
-            return (ys, None) if return_logp else ys
-        from .decode_ops import argmax_rows
-        from .gen_ops import gen_log_softmax
-        with torch.no_grad():
-            m.process_data(data)
-            enc, _, _, _, _ = m.encode(data)
-            if self.graph and enc.is_cuda:
-                return self._forward_graph(data, enc, return_logp)
-            B, T = enc.size(0), self.max_tgt_len
-            if self.eos_id is not None:  # the device-stepped step run eagerly, as the other two generators do
-                e = self._state(m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True), bool(return_logp))
-                self._reset(e)
-                return self._decode(e, False)
-            cache = m.decoder.make_cache(enc, data.src_mask, T, repeat_heads=True)  # as CSATrans.decode masks
-            ys = torch.zeros(B, T, dtype=torch.long, device=enc.device)
-            ys[:, 0] = self.start_pos
-            logps = []
-            con = self.constraints
-            suppress = None if con is None else con.suppress_tensor(enc.device)
-            for t in range(T - 1):
-                x = m.tgt_embedding.step(ys[:, t:t + 1], t)
-                dec = m.decoder.step(x, cache, t)
-                logits = m.generator.linear(dec[:, 0])
-                if con is not None:
-                    con.apply(logits, ys, t, suppress=suppress)
-                argmax_rows(logits, out=ys[:, t + 1], is_pad=cache.pad[:, t + 1], pad_id=PAD)
-                if return_logp:
-                    logps.append(gen_log_softmax(logits, 0.0))
-            self.last_steps_run = self.last_replays = T - 1
-            out = ys[:, 1:]
-            return (out, torch.stack(logps)) if return_logp else out
-
-    # ---- graph=True: the device-stepped decode step that _SteppedDecoding captures and replays ----
-
-    def _state(self, cache, return_logp):
-        """The static buffers beside the cache: tokens, the step counter, and the slot where each replay leaves its
-        log-probabilities when return_logp asks for them."""
-        B, T = cache.pad.shape
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=cache.pad.device)
-        return SimpleNamespace(cache=cache, ys=z(B, T, dtype=torch.long), t_dev=z(1, dtype=torch.int32), logp=None,
-                               return_logp=return_logp, suppress=self._suppress_state(cache.pad.device),
-                               fin=z(B, dtype=torch.uint8) if self.eos_id is not None else None,
-                               stop=self._stop_state(cache.pad.device), stop_host=None)
-
-    def _device_step(self, e):
-        """One decode step with every step-dependent index read from e.t_dev on the device: the same launches for
-        every t, so they can be captured once. Ends by advancing the counter, after its last reader."""
-        from .decode_ops import argmax_rows
-        from .gen_ops import gen_log_softmax
-        m = self.model
-        x = m.tgt_embedding.step(e.ys, e.t_dev)
-        dec = m.decoder.step(x, e.cache, e.t_dev)
-        logits = m.generator.linear(dec[:, 0])
-        if self.constraints is not None:  # with eos_id, a finished row takes PAD whatever its logits: left alone
-            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
-        if e.fin is None:
-            argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad)
-        else:
-            argmax_rows(logits, out=e.ys, is_pad=e.cache.pad, pad_id=PAD, t_dev=e.t_dev, head_pad=e.cache.head_pad,
-                        fin=e.fin, eos_id=self.eos_id)
-        e.logp = gen_log_softmax(logits, 0.0) if e.return_logp else None
-        self._advance(e)
-
-    def _reset(self, e):
-        """Step 0 of a new batch. The self-attention cache needs no reset: rows above t are never read."""
-        e.ys.zero_()
-        e.ys[:, 0] = self.start_pos
-        e.cache.pad.zero_()
-        e.cache.head_pad.zero_()
-        if e.fin is not None:
-            e.fin.zero_()
-        if e.stop is not None:
-            e.stop.zero_()
-        e.t_dev.zero_()
-
-    def _eos_key(self):
-        """What eos_id adds to the graph key extras: nothing without one."""
-        return () if self.eos_id is None else ("eos", int(self.eos_id))
-
-    def _forward_graph(self, data, enc, return_logp):
-        return_logp = bool(return_logp)
-        extras = (return_logp, *self._constraint_key(), *self._eos_key(), *self._stop_key())
-        return self._decode(self._graph_entry(enc, data.src_mask, extras, return_logp=return_logp), True)
-
-    def _decode(self, e, graphed):
-        """The steps of one call on the reset state e; each step's log-probabilities are copied out of their slot as
-        the step is issued, and those of the steps that ran are returned."""
-        logps = []
-        self._run_steps(e, graphed, (lambda: logps.append(e.logp.clone())) if e.return_logp else None)
-        out = e.ys[:, 1:].clone()
-        return (out, torch.stack(logps[:self.last_steps_run])) if e.return_logp else out
-
-
-class BeamSearchGenerator(_SteppedDecoding, nn.Module):
-    """Beam search of width W = beam_size over the KV-cached, device-stepped decode step (no counterpart in the
-    reference, whose only strategy is GreedyGenerator).
-
-    Rows are R = B * W hypotheses, row r = b * W + w. All max_tgt_len - 1 steps run (static shapes) unless
-    early_stop=True (_SteppedDecoding) ends the call once every hypothesis has finished; the result is bitwise the same.
-    cum (fp32) starts at 0 for row b * W and -inf for the other W - 1 rows, all tokens BOS. Per step the eval-mode
-    generator logits z give logp = z - lse (fp32) and a candidate scores cum[r] + (z - lse[r]); a hypothesis that has
-    emitted eos_id is finished (None: never), offers the single candidate (cum, PAD), and its row still runs through
-    the decoder, ignored. Per AST the best W candidates survive: score descending, then parent row, then token.
-    The self-attention key mask is the hypothesis' own PAD columns (make_std_mask per row, DecodeCache without
-    repeat_heads): the reference decode()'s `.repeat(num_heads, 1, 1)` would let a finished hypothesis' padding mask
-    keys of live ones, so it is not reproduced here.
-
-    Nothing is gathered between steps: the K/V cache stays where each step stored it and the attention follows the
-    (R, T) ancestry table that the selection rewrites (decode_ops.beam_row_topk / beam_select, decode_attention's anc=
-    and kv_group=); the W hypotheses of an AST share one memory projection. The step index lives in a 4-byte device
-    counter, so the launches of a step never depend on it.
-
-    After the last step the W hypotheses of an AST are ranked by cum / len ** length_penalty, len counting tokens up
-    to and including the first EOS (max_tgt_len - 1 without one). forward returns the best ids (B, max_tgt_len - 1),
-    PAD after EOS; with return_all also the ids (B, W, max_tgt_len - 1) and scores (B, W) in rank order.
-
-    graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
-    (..., beam_size, ...) (_SteppedDecoding); bitwise the eager result. Inference only: a model in training mode
-    raises.
-
-    constraints=DecodingConstraints(...): every live hypothesis' logits go through decode_ops.constrain_rows (its own
-    history, as the selection rewrote it) before the row top-W; a banned token is a -inf logit, so lse and the scores
-    are those of the distribution renormalised over what is left. Finished hypotheses are left alone."""
-
-    def __init__(self, model, max_tgt_len, beam_size, length_penalty=0.0, eos_id=EOS, multi_gpu=False, graph=False,
-                 constraints=None, early_stop=False):
-        super().__init__()
-        if not 1 <= beam_size <= 8:
-            raise ValueError("BeamSearchGenerator: beam_size must be in [1, 8]")
-        if max_tgt_len < 2:
-            raise ValueError("BeamSearchGenerator: max_tgt_len must be at least 2")
-        self.model = model.module if multi_gpu else model
-        self.max_tgt_len = max_tgt_len
-        self.beam_size = beam_size
-        self.length_penalty = float(length_penalty)
-        self.eos_id = eos_id
-        self.start_pos = BOS
-        self._init_stepped(graph, early_stop, beam=beam_size)
-        self.constraints = constraints
-
-    def forward(self, data, return_all=False):
-        m = self.model
-        self._check_eval()
-        with torch.no_grad():
-            m.process_data(data)
-            enc, _, _, _, _ = m.encode(data)
-            return self.search(enc, data.src_mask, return_all)
-
-    def search(self, enc, src_mask=None, return_all=False):
-        """The decoder side alone: enc (B, S, E) batch-first memory (any source, CPU included), src_mask (B, S) bool
-        key-padding mask or None."""
-        self._check_eval()
-        V = self.model.generator.linear.weight.shape[0]
-        if V < self.beam_size:
-            raise ValueError("BeamSearchGenerator: the target vocabulary is smaller than the beam")
-        with torch.no_grad():
-            if self.graph and enc.is_cuda:
-                e = self._graph_entry(enc, src_mask, (self.beam_size, *self._constraint_key(), *self._stop_key()))
-                self._run_steps(e, True)
-            else:
-                cache = self.model.decoder.make_cache(enc, src_mask, self.max_tgt_len, beam=self.beam_size)
-                e = self._state(cache)
-                self._reset(e)
-                self._run_steps(e, False)
-            return self._rank(e, enc.size(0), return_all)
-
-    def _check_eval(self):
-        if self.model.training:
-            raise RuntimeError("BeamSearchGenerator: inference only (the model is in training mode)")
-
-    def _state(self, cache):
-        """The per-hypothesis state beside the cache: tokens, cumulative log-probability, finished flag, the step
-        counter and the row top-W buffers."""
-        R, T, W, dev = cache.pad.shape[0], self.max_tgt_len, self.beam_size, cache.pad.device
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
-        return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), cum=z(R, dtype=torch.float32),
-                               fin=z(R, dtype=torch.uint8), t_dev=z(1, dtype=torch.int32),
-                               lse=z(R, dtype=torch.float32), topv=z(R, W, dtype=torch.float32),
-                               topi=z(R, W, dtype=torch.int32), suppress=self._suppress_state(dev),
-                               stop=self._stop_state(dev), stop_host=None)
-
-    def _reset(self, e):
-        """Step 0 of a new batch: BOS everywhere, one live hypothesis per AST. The self-attention cache needs no
-        reset (rows above t are never read); the ancestry table is cleared so that every entry stays a valid row."""
-        e.ys.zero_()
-        e.ys[:, 0] = self.start_pos
-        e.cache.pad.zero_()
-        e.cache.anc.zero_()
-        e.cum.fill_(float("-inf"))
-        e.cum.view(-1, self.beam_size)[:, 0] = 0.0
-        e.fin.zero_()
-        if e.stop is not None:
-            e.stop.zero_()
-        e.t_dev.zero_()
-
-    def _device_step(self, e):
-        """One beam step with every step-dependent index read from e.t_dev (on the device where the kernels run): the
-        same launches for every t. Ends by advancing the counter, after its last reader."""
-        from .decode_ops import beam_row_topk, beam_select
-        m, T = self.model, self.max_tgt_len
-        x = m.tgt_embedding.step(e.ys, e.t_dev)
-        dec = m.decoder.step(x, e.cache, e.t_dev)
-        logits = m.generator.linear(dec[:, 0])
-        if self.constraints is not None:  # a finished hypothesis offers (cum, PAD) whatever its logits: left alone
-            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
-        beam_row_topk(logits, self.beam_size, e.lse, e.topv, e.topi, t_dev=e.t_dev, t_end=T - 1)
-        beam_select(e.topv, e.topi, e.lse, e.cum, e.fin, e.ys, e.cache.pad, e.cache.anc, e.t_dev, eos_id=self.eos_id,
-                    pad_id=PAD)
-        self._advance(e)
-
-    def _rank(self, e, B, return_all):
-        W, T = self.beam_size, self.max_tgt_len
-        ids = e.ys[:, 1:]
-        length = torch.full((B * W,), T - 1, dtype=torch.long, device=ids.device)
-        if self.eos_id is not None:
-            is_eos = ids == self.eos_id
-            length = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, length)
-        score = e.cum.clone() if self.length_penalty == 0.0 else e.cum / length.float() ** self.length_penalty
-        score = score.view(B, W)
-        order = torch.argsort(score, dim=1, descending=True, stable=True)
-        ranked = ids.reshape(B, W, T - 1).gather(1, order[:, :, None].expand(B, W, T - 1))
-        best = ranked[:, 0].clone()
-        return (best, ranked, score.gather(1, order)) if return_all else best
-
-    def _check_capture(self, enc):
-        from ._lib import lib
-        if not lib().csa_beam_supported(self.beam_size, self.max_tgt_len) or enc.dtype != torch.float32:
-            raise ValueError("BeamSearchGenerator: graph=True needs fp32 and max_tgt_len <= 256 (csa_beam_supported)")
-        self._check_constraints_capture(enc)
-
-
-class SamplingGenerator(_SteppedDecoding, nn.Module):
-    """Sampled decoding over the KV-cached, device-stepped decode step: num_samples independent draws per AST from the
-    model's distribution, filtered by temperature, top_k (0: off) and top_p (>= 1: off), with the log-probability of
-    every drawn token (no counterpart in the reference, whose only strategy is GreedyGenerator).
-
-    Rows are R = B * num_samples, row r = b * num_samples + s. Each row keeps its own self-attention cache row (no
-    ancestry table); the rows of an AST share one memory projection and mask (DecodeCache kv_group, make_cache's
-    group=). The self-attention key mask is the row's own PAD columns, as in BeamSearchGenerator and for its reason:
-    the reference decode()'s `.repeat(num_heads, 1, 1)` would let a finished sample's padding mask keys of live ones.
-    Per step the eval-mode generator logits go through decode_ops.sample_rows (csrc/csa_sample.hip): y = z /
-    temperature, top-k with all ties, top-p on the renormalised top-k set (tie-inclusive), one Gumbel-max draw from
-    Philox stream 7 keyed by (seed, row, step, column), logp = y[token] - lse(y over the kept set). A row that has
-    emitted eos_id is finished (None: never): it takes PAD with logp 0 and still runs through the decoder, ignored.
-    All max_tgt_len - 1 steps run (static shapes) unless early_stop=True (_SteppedDecoding) ends the call once every row
-    has finished; ids and log-probabilities are bitwise the same.
-
-    forward(data, seed=None, return_logp=False) / sample(enc, src_mask, seed, return_logp) return the ids
-    (B, max_tgt_len - 1), or (B, num_samples, max_tgt_len - 1) when num_samples > 1, PAD after EOS; with return_logp
-    also the per-token log-probabilities of the same shape, 0 after EOS, whose sum over the last dim is the sequence
-    log-probability under the sampled (filtered) distribution. seed: a 64-bit key; None draws one from torch's CPU
-    generator (reproducible under torch.manual_seed). The same seed repeats the same draws on any device path.
-
-    graph=True (CUDA model): as CachedGreedyGenerator, the step is replayed from one captured graph per
-    (..., temperature, top_k, top_p, num_samples, eos_id, return_logp, ...) (_SteppedDecoding); the seed lives in a
-    16-byte device buffer filled outside the graph, so a replay draws anew. Bitwise the eager result. Inference only:
-    a model in training mode raises.
-
-    constraints=DecodingConstraints(...): every live row's logits go through decode_ops.constrain_rows before
-    sample_rows, which never draws a -inf entry and renormalises: logp is the log-probability under the constrained,
-    filtered distribution. Finished rows are left alone."""
-
-    def __init__(self, model, max_tgt_len, temperature=1.0, top_k=0, top_p=1.0, num_samples=1, eos_id=EOS,
-                 multi_gpu=False, graph=False, constraints=None, early_stop=False):
-        super().__init__()
-        if not float(temperature) > 0.0:
-            raise ValueError("SamplingGenerator: temperature must be positive")
-        if int(top_k) != top_k or top_k < 0:
-            raise ValueError("SamplingGenerator: top_k must be a non-negative integer (0 turns it off)")
-        if not float(top_p) > 0.0:
-            raise ValueError("SamplingGenerator: top_p must be positive (1 or more turns it off)")
-        if int(num_samples) != num_samples or num_samples < 1:
-            raise ValueError("SamplingGenerator: num_samples must be a positive integer")
-        if max_tgt_len < 2:
-            raise ValueError("SamplingGenerator: max_tgt_len must be at least 2")
-        self.model = model.module if multi_gpu else model
-        self.max_tgt_len = max_tgt_len
-        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
-        self.num_samples = int(num_samples)
-        self.eos_id = eos_id
-        self.start_pos = BOS
-        self._init_stepped(graph, early_stop, group=self.num_samples)
-        self.constraints = constraints
-
-    def forward(self, data, seed=None, return_logp=False):
-        m = self.model
-        self._check_eval()
-        with torch.no_grad():
-            m.process_data(data)
-            enc, _, _, _, _ = m.encode(data)
-            return self.sample(enc, data.src_mask, seed, return_logp)
-
-    def sample(self, enc, src_mask=None, seed=None, return_logp=False):
-        """The decoder side alone: enc (B, S, E) batch-first memory (any source, CPU included), src_mask (B, S) bool
-        key-padding mask or None."""
-        self._check_eval()
-        return_logp = bool(return_logp)
-        if seed is None:  # one 64-bit Philox key per call from torch's global CPU generator, as ops._draw_seed
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        key = torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed, 0], dtype=torch.int64)  # {seed, offset}
-        T = self.max_tgt_len
-        with torch.no_grad():
-            if self.graph and enc.is_cuda:
-                extras = (self.temperature, self.top_k, self.top_p, self.num_samples, self.eos_id, return_logp,
-                          *self._constraint_key(), *self._stop_key())
-                e = self._graph_entry(enc, src_mask, extras, return_logp=return_logp)
-                e.rng.copy_(key)  # outside the graph: the replays read it on the device
-                self._run_steps(e, True)
-            else:
-                cache = self.model.decoder.make_cache(enc, src_mask, T, group=self.num_samples)
-                e = self._state(cache, return_logp)
-                self._reset(e)
-                e.rng.copy_(key)
-                self._run_steps(e, False)
-            shape = (enc.size(0), T - 1) if self.num_samples == 1 else (enc.size(0), self.num_samples, T - 1)
-            ids = e.ys[:, 1:].reshape(shape).clone()
-            return (ids, e.logp.reshape(shape).clone()) if return_logp else ids
-
-    def _check_eval(self):
-        if self.model.training:
-            raise RuntimeError("SamplingGenerator: inference only (the model is in training mode)")
-
-    def _state(self, cache, return_logp):
-        """The per-row state beside the cache: tokens, finished flag, the step counter, the {seed, offset} key that the
-        kernel reads on the device and, when asked for, the per-token log-probabilities."""
-        R, T, dev = cache.pad.shape[0], self.max_tgt_len, cache.pad.device
-        z = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype, device=dev)
-        return SimpleNamespace(cache=cache, ys=z(R, T, dtype=torch.long), fin=z(R, dtype=torch.uint8),
-                               t_dev=z(1, dtype=torch.int32), rng=z(2, dtype=torch.int64),
-                               logp=z(R, T - 1, dtype=torch.float32) if return_logp else None,
-                               suppress=self._suppress_state(dev), stop=self._stop_state(dev), stop_host=None)
-
-    def _reset(self, e):
-        """Step 0 of a new batch: BOS everywhere, no row finished. The self-attention cache needs no reset (rows above t
-        are never read)."""
-        e.ys.zero_()
-        e.ys[:, 0] = self.start_pos
-        e.cache.pad.zero_()
-        e.fin.zero_()
-        if e.logp is not None:
-            e.logp.zero_()
-        if e.stop is not None:
-            e.stop.zero_()
-        e.t_dev.zero_()
-
-    def _device_step(self, e):
-        """One sampling step with every step-dependent index read from e.t_dev (on the device where the kernels run):
-        the same launches for every t. Ends by advancing the counter, after its last reader."""
-        from .decode_ops import sample_rows
-        m = self.model
-        x = m.tgt_embedding.step(e.ys, e.t_dev)
-        dec = m.decoder.step(x, e.cache, e.t_dev)
-        logits = m.generator.linear(dec[:, 0])
-        if self.constraints is not None:  # a finished row takes PAD whatever its logits: left alone
-            self.constraints.apply(logits, e.ys, e.t_dev, fin=e.fin, suppress=e.suppress)
-        sample_rows(logits, e.ys, e.cache.pad, e.fin, e.t_dev, e.rng, temperature=self.temperature, top_k=self.top_k,
-                    top_p=self.top_p, eos_id=self.eos_id, pad_id=PAD, logp=e.logp)
-        self._advance(e)
-
-    def _check_capture(self, enc):
-        from ._lib import lib
-        V = self.model.generator.linear.weight.shape[0]
-        if not lib().csa_sample_rows_supported(V) or enc.dtype != torch.float32:
-            raise ValueError("SamplingGenerator: graph=True needs fp32 and a target vocabulary of at most 32768 "
-                             "(csa_sample_rows_supported)")
-        self._check_constraints_capture(enc)
+_DECODING = ("DecodingConstraints", "_SteppedDecoding", "CachedGreedyGenerator", "BeamSearchGenerator",
+             "SamplingGenerator")
+
+
+def __getattr__(name):
+    """The names of csa_amd.decoding, exported from here as before they moved. That module imports this one
+    (CachedGreedyGenerator subclasses GreedyGenerator), so it is imported on first use, not while this one loads."""
+    if name in _DECODING:
+        from . import decoding
+        return getattr(decoding, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 class _GatherTargets(torch.autograd.Function):

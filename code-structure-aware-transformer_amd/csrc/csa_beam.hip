@@ -26,6 +26,7 @@
 // writes: an AST's rows belong to one workgroup, so two children of one parent and a swap of two rows come out right
 // in place. LDS: 13 W T bytes at the limits W = 8, T = 256 (csa_beam_supported).
 #include "csa_common.hpp"
+#include "csa_row_select.hpp"
 #include "../../include/csa_hip.h"
 
 #include <math.h>
@@ -37,19 +38,6 @@ namespace {
 constexpr int BEAM_THREADS = 256;
 constexpr int BEAM_MAX_W = 8;
 constexpr int BEAM_MAX_T = 256;
-constexpr int NO_IDX = 0x7fffffff;  // "no entry": loses every tie against a real index
-
-// (v, i) comes before (vo, io): the larger value, then the lower index
-__device__ __forceinline__ bool ahead(float v, int i, float vo, int io) { return v > vo || (v == vo && i < io); }
-
-// (m, s) <- the online (max, sum exp) of the union of (m, s) and (mo, so); a side with m = -inf holds nothing
-__device__ __forceinline__ void lse_merge(float& m, float& s, float mo, float so) {
-  const float mn = fmaxf(m, mo);
-  const float a = (m > -INFINITY) ? s * expf(m - mn) : 0.f;
-  const float b = (mo > -INFINITY) ? so * expf(mo - mn) : 0.f;
-  m = mn;
-  s = a + b;
-}
 
 template <int WM>
 __global__ __launch_bounds__(BEAM_THREADS) void k_beam_row_topk(const float* __restrict__ z, int64_t V, int W,
@@ -262,22 +250,6 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_select(const SelArgs a) {
   }
 }
 
-csa_status bfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al(const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
-csa_status launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("%s: %s", fn, hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -288,13 +260,13 @@ int csa_beam_supported(int64_t W, int64_t T) {
 
 csa_status csa_beam_row_topk(const float* z, int64_t rows, int64_t V, int64_t W, float* lse, float* topv, int32_t* topi,
                              const int32_t* t_dev, int64_t t_end, void* stream) {
-  if (W < 1 || W > BEAM_MAX_W) return bfail(CSA_UNSUPPORTED_SHAPE, "csa_beam_row_topk: W must be in [1, 8]");
+  if (W < 1 || W > BEAM_MAX_W) return fail(CSA_UNSUPPORTED_SHAPE, "csa_beam_row_topk: W must be in [1, 8]");
   if (rows < 0 || rows > 0x7fffffff || V < 1 || V >= 0x7fffffff || t_end < 0 || t_end > 0x7fffffff)
-    return bfail(CSA_INVALID_ARG, "csa_beam_row_topk: bad rows / V / t_end");
-  if (V < W) return bfail(CSA_INVALID_ARG, "csa_beam_row_topk: V must be at least W");
-  if (!z || !lse || !topv || !topi) return bfail(CSA_INVALID_ARG, "csa_beam_row_topk: null pointer");
-  if (!al(z, 4) || !al(lse, 4) || !al(topv, 4) || !al(topi, 4) || !al(t_dev, 4))
-    return bfail(CSA_INVALID_ARG, "csa_beam_row_topk: misaligned pointer (4 bytes each)");
+    return fail(CSA_INVALID_ARG, "csa_beam_row_topk: bad rows / V / t_end");
+  if (V < W) return fail(CSA_INVALID_ARG, "csa_beam_row_topk: V must be at least W");
+  if (!z || !lse || !topv || !topi) return fail(CSA_INVALID_ARG, "csa_beam_row_topk: null pointer");
+  if (!aligned(z, 4) || !aligned(lse, 4) || !aligned(topv, 4) || !aligned(topi, 4) || !aligned(t_dev, 4))
+    return fail(CSA_INVALID_ARG, "csa_beam_row_topk: misaligned pointer (4 bytes each)");
   if (rows == 0) return CSA_OK;
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
@@ -310,16 +282,16 @@ csa_status csa_beam_row_topk(const float* z, int64_t rows, int64_t V, int64_t W,
 }
 
 csa_status csa_beam_select(const csa_beam_select_args* a, void* stream) {
-  if (!a) return bfail(CSA_INVALID_ARG, "csa_beam_select: null args");
+  if (!a) return fail(CSA_INVALID_ARG, "csa_beam_select: null args");
   if (!csa_beam_supported(a->W, a->T))
-    return bfail(CSA_UNSUPPORTED_SHAPE, "csa_beam_select: W must be in [1, 8] and T in [2, 256]");
+    return fail(CSA_UNSUPPORTED_SHAPE, "csa_beam_select: W must be in [1, 8] and T in [2, 256]");
   if (a->B < 0 || a->B * a->W > 0x7fffffff || a->tok_stride < a->T || a->pad_stride < a->T || a->anc_stride < a->T)
-    return bfail(CSA_INVALID_ARG, "csa_beam_select: bad B or a row stride below T");
+    return fail(CSA_INVALID_ARG, "csa_beam_select: bad B or a row stride below T");
   if (!a->topv || !a->topi || !a->lse || !a->cum || !a->fin || !a->tokens || !a->pad || !a->anc || !a->t_dev)
-    return bfail(CSA_INVALID_ARG, "csa_beam_select: null pointer");
-  if (!al(a->topv, 4) || !al(a->topi, 4) || !al(a->lse, 4) || !al(a->cum, 4) || !al(a->tokens, 8) || !al(a->anc, 4) ||
-      !al(a->parent, 4) || !al(a->t_dev, 4))
-    return bfail(CSA_INVALID_ARG, "csa_beam_select: misaligned pointer (tokens 8, the fp32 / int32 arrays 4 bytes)");
+    return fail(CSA_INVALID_ARG, "csa_beam_select: null pointer");
+  if (!aligned(a->topv, 4) || !aligned(a->topi, 4) || !aligned(a->lse, 4) || !aligned(a->cum, 4) ||
+      !aligned(a->tokens, 8) || !aligned(a->anc, 4) || !aligned(a->parent, 4) || !aligned(a->t_dev, 4))
+    return fail(CSA_INVALID_ARG, "csa_beam_select: misaligned pointer (tokens 8, the fp32 / int32 arrays 4 bytes)");
   if (a->B == 0) return CSA_OK;
   SelArgs d;
   d.W = (int)a->W; d.T = (int)a->T;

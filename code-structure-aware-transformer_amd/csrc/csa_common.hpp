@@ -26,6 +26,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "../../include/csa_hip.h"
+
 namespace csa {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -421,5 +423,20 @@ struct SideLane {
 // Per-thread last-error text shared by every translation unit (csa_last_error_str).
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* get_error();
+
+// `return fail(status, "fn: what is wrong");` of an entry point's validation.
+inline csa_status fail(csa_status s, const char* msg) {
+  set_error("%s", msg);
+  return s;
+}
+// After an entry point's launches: CSA_OK, or CSA_LAUNCH_FAILED with "<fn>: <hip error string>".
+inline csa_status launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return CSA_OK;
+  set_error("%s: %s", fn, hipGetErrorString(e));
+  return CSA_LAUNCH_FAILED;
+}
+// p is a multiple of n bytes (n a power of two); a null pointer is.
+inline bool aligned(const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
 
 }  // namespace csa

@@ -96,13 +96,6 @@ __global__ __launch_bounds__(CON_THREADS) void k_constrain_rows(const ConArgs a)
   }
 }
 
-csa_status cfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al(const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -110,23 +103,23 @@ extern "C" {
 int csa_constrain_rows_supported(int64_t T) { return (T >= 2 && T <= CON_MAX_T) ? 1 : 0; }
 
 csa_status csa_constrain_rows(const csa_constrain_rows_args* a, void* stream) {
-  if (!a) return cfail(CSA_INVALID_ARG, "csa_constrain_rows: null args");
-  if (!a->logits || !a->ys) return cfail(CSA_INVALID_ARG, "csa_constrain_rows: null pointer (logits, ys)");
+  if (!a) return fail(CSA_INVALID_ARG, "csa_constrain_rows: null args");
+  if (!a->logits || !a->ys) return fail(CSA_INVALID_ARG, "csa_constrain_rows: null pointer (logits, ys)");
   if (!(a->repetition_penalty > 0.f) || !(a->repetition_penalty < INFINITY))
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: repetition_penalty must be in (0, inf) (1 turns it off)");
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: repetition_penalty must be in (0, inf) (1 turns it off)");
   if (a->rows < 0 || a->rows > 0x7fffffff || a->V < 0 || a->T < 0 || a->no_repeat_ngram < 0 || a->min_length < 0 ||
       a->n_suppress < 0)
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: negative size (rows, V, T, no_repeat_ngram, min_length, n_suppress)");
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: negative size (rows, V, T, no_repeat_ngram, min_length, n_suppress)");
   if (a->n_suppress > CON_MAX_SUPPRESS)
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: the suppress list holds at most 256 ids");
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: the suppress list holds at most 256 ids");
   if (a->n_suppress > 0 && !a->suppress)
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: null pointer (suppress with n_suppress > 0)");
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: null pointer (suppress with n_suppress > 0)");
   if (a->logits_stride < a->V || a->ys_stride < a->T)
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: a row stride below V (logits) or T (ys)");
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: a row stride below V (logits) or T (ys)");
   if (!csa_constrain_rows_supported(a->T))
-    return cfail(CSA_UNSUPPORTED_SHAPE, "csa_constrain_rows: T must be in [2, 1024]");
-  if (!al(a->logits, 4) || !al(a->ys, 8) || !al(a->suppress, 4) || !al(a->t_dev, 4))
-    return cfail(CSA_INVALID_ARG, "csa_constrain_rows: misaligned pointer (tokens 8, the fp32 / int32 arrays 4 bytes)");
+    return fail(CSA_UNSUPPORTED_SHAPE, "csa_constrain_rows: T must be in [2, 1024]");
+  if (!aligned(a->logits, 4) || !aligned(a->ys, 8) || !aligned(a->suppress, 4) || !aligned(a->t_dev, 4))
+    return fail(CSA_INVALID_ARG, "csa_constrain_rows: misaligned pointer (tokens 8, the fp32 / int32 arrays 4 bytes)");
   if (a->rows == 0 || a->V == 0) return CSA_OK;
   ConArgs d;
   d.z = a->logits; d.z_s = a->logits_stride; d.V = a->V;
@@ -141,12 +134,7 @@ csa_status csa_constrain_rows(const csa_constrain_rows_args* a, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   hipLaunchKernelGGL(k_constrain_rows, dim3((unsigned)a->rows), dim3(CON_THREADS), 0, st, d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_constrain_rows: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_constrain_rows");
 }
 
 }  // extern "C"

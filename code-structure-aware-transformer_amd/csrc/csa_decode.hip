@@ -80,11 +80,6 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // The cache row that holds key j of this hypothesis, clamped into [0, B): a bad table reads a wrong row, never
 // outside the cache.
@@ -168,7 +163,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decode_attn(const DecArgs a)
     ps[w][lane] = p;
     __syncthreads();
     if (live) {
-      l = l * alpha + wave_sum(p);
+      l = l * alpha + ln_wave_sum(p);
       m = mn;
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] *= alpha;
@@ -388,12 +383,6 @@ __global__ __launch_bounds__(256) void k_decode_embed(const int64_t* __restrict_
   ln_row_fwd<CPL>(v, lane, E, eps, gamma, beta, x + row * E, mean, rstd);
 }
 
-csa_status dfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 inline bool m4(int64_t s) { return s % 4 == 0; }
 
 // csa_decode_attn (step == false: host t, len = key count) and csa_decode_attn_step (step == true: t read from
@@ -413,7 +402,7 @@ csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool 
   if (append && (!a->k_new || !a->v_new)) return fail(CSA_INVALID_ARG, "k_new and v_new go together");
   if (step) {
     if (!append) return fail(CSA_INVALID_ARG, "k_new and v_new are required");
-    if (!t_dev || (((uintptr_t)t_dev) & 3)) return fail(CSA_INVALID_ARG, "t_dev must be a 4-byte aligned device pointer");
+    if (!t_dev || !aligned(t_dev, 4)) return fail(CSA_INVALID_ARG, "t_dev must be a 4-byte aligned device pointer");
   } else if (append && (a->t < 0 || a->t + 1 != a->len)) {
     return fail(CSA_INVALID_ARG, "append mode needs len == t + 1");
   }
@@ -422,12 +411,13 @@ csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool 
       return fail(CSA_INVALID_ARG, "kv_group must be positive and divide the row count B");
     if (anc && (kv_group != 1 || !append))
       return fail(CSA_INVALID_ARG, "an ancestry table goes with append mode and kv_group == 1");
-    if (anc && ((((uintptr_t)anc) & 3) || anc_stride < a->len))
+    if (anc && (!aligned(anc, 4) || anc_stride < a->len))
       return fail(CSA_INVALID_ARG, "anc must be 4-byte aligned with a row stride >= len");
   }
   if (a->B == 0) return CSA_OK;
   if (!a->q || !a->K || !a->V || !a->out) return fail(CSA_INVALID_ARG, "null pointer");
-  if (!al16(a->q) || !al16(a->K) || !al16(a->V) || !al16(a->out) || !al16(a->k_new) || !al16(a->v_new) ||
+  if (!aligned(a->q, 16) || !aligned(a->K, 16) || !aligned(a->V, 16) || !aligned(a->out, 16) || !aligned(a->k_new, 16) ||
+      !aligned(a->v_new, 16) ||
       !m4(a->q_sb) || !m4(a->q_sh) || !m4(a->k_sb) || !m4(a->k_sh) || !m4(a->k_sn) || !m4(a->v_sb) || !m4(a->v_sh) ||
       !m4(a->v_sn) || (append && (!m4(a->kn_sb) || !m4(a->kn_sh) || !m4(a->vn_sb) || !m4(a->vn_sh))))
     return fail(CSA_INVALID_ARG, "pointers must be 16-byte aligned and strides multiples of 4 elements");
@@ -451,12 +441,33 @@ csa_status decode_attn_impl(const char* fn, const csa_decode_attn_args* a, bool 
     hipLaunchKernelGGL(k_decode_attn<true>, grid, dim3(64 * DEC_WAVES), 0, st, d);
   else
     hipLaunchKernelGGL(k_decode_attn<false>, grid, dim3(64 * DEC_WAVES), 0, st, d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("%s: %s", fn, hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched(fn);
+}
+
+// csa_argmax_rows_step and csa_argmax_rows_fin_step (with_fin: the finished flags and eos_id): one validation, the
+// entry point's own kernel.
+csa_status argmax_step_impl(const char* fn, const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride,
+                            int64_t T, uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
+                            bool with_fin, uint8_t* fin, int64_t eos_id, const int32_t* t_dev, void* stream) {
+  const auto fail = [fn](csa_status s, const char* m) {
+    csa::set_error("%s: %s", fn, m);
+    return s;
+  };
+  if (rows < 0 || V < 1 || rows > 0x7fffffff || T < 1 || ys_stride < T || (pad && pad_stride < T) ||
+      (head_pad && (H < 1 || H > 0x7fffffff)))
+    return fail(CSA_INVALID_ARG, "bad rows / V / T / strides / H");
+  if (!x || !ys || (with_fin && !fin) || !t_dev) return fail(CSA_INVALID_ARG, "null pointer");
+  if (!aligned(x, 4) || !aligned(ys, 8) || !aligned(t_dev, 4)) return fail(CSA_INVALID_ARG, "misaligned pointer");
+  if (rows == 0) return CSA_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  const DeviceGuard guard(st);
+  if (with_fin)
+    hipLaunchKernelGGL(k_argmax_rows_fin_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad,
+                       pad_stride, head_pad, (int)H, pad_id, fin, eos_id, t_dev);
+  else
+    hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad,
+                       pad_stride, head_pad, (int)H, pad_id, t_dev);
+  return launched(fn);
 }
 
 }  // namespace
@@ -482,12 +493,13 @@ csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int
                             const float* W, int64_t vocab, const float* pe, int64_t max_len, const float* gamma,
                             const float* beta, float eps, float* x, int64_t E, void* stream) {
   const int cpl = ln_cpl(E);
-  if (cpl == 0) return dfail(CSA_UNSUPPORTED_SHAPE, "csa_decode_embed: E must be a multiple of 4 in [4, 1024]");
+  if (cpl == 0) return fail(CSA_UNSUPPORTED_SHAPE, "csa_decode_embed: E must be a multiple of 4 in [4, 1024]");
   if (B < 0 || B > 0x7fffffff || T < 1 || vocab < 1 || (pe && max_len < 1) || ys_stride < T)
-    return dfail(CSA_INVALID_ARG, "csa_decode_embed: bad B / T / vocab / max_len / ys_stride");
-  if (!ys || !t_dev || !W || !gamma || !beta || !x) return dfail(CSA_INVALID_ARG, "csa_decode_embed: null pointer");
-  if ((((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3) || !al16(W) || !al16(pe) || !al16(gamma) || !al16(beta) || !al16(x))
-    return dfail(CSA_INVALID_ARG, "csa_decode_embed: misaligned pointer (ys 8, t_dev 4, the fp32 rows 16 bytes)");
+    return fail(CSA_INVALID_ARG, "csa_decode_embed: bad B / T / vocab / max_len / ys_stride");
+  if (!ys || !t_dev || !W || !gamma || !beta || !x) return fail(CSA_INVALID_ARG, "csa_decode_embed: null pointer");
+  if (!aligned(ys, 8) || !aligned(t_dev, 4) || !aligned(W, 16) || !aligned(pe, 16) || !aligned(gamma, 16) ||
+      !aligned(beta, 16) || !aligned(x, 16))
+    return fail(CSA_INVALID_ARG, "csa_decode_embed: misaligned pointer (ys 8, t_dev 4, the fp32 rows 16 bytes)");
   if (B == 0) return CSA_OK;
   const int64_t t_end = (pe && max_len < T) ? max_len : T;
   const hipStream_t st = (hipStream_t)stream;
@@ -503,91 +515,46 @@ csa_status csa_decode_embed(const int64_t* ys, int64_t ys_stride, int64_t B, int
     default: CSA_EMBED_LAUNCH(4);
   }
 #undef CSA_EMBED_LAUNCH
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_decode_embed: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_decode_embed");
 }
 
 csa_status csa_argmax_rows(const float* x, int64_t rows, int64_t V, int64_t* idx, int64_t idx_stride, uint8_t* is_pad,
                            int64_t pad_stride, int64_t pad_id, float* maxval, void* stream) {
-  if (rows < 0 || V < 1 || rows > 0x7fffffff) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: bad rows / V");
-  if (!x || !idx) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: null pointer");
-  if ((((uintptr_t)x) & 3) || (((uintptr_t)idx) & 7)) return dfail(CSA_INVALID_ARG, "csa_argmax_rows: misaligned pointer");
+  if (rows < 0 || V < 1 || rows > 0x7fffffff) return fail(CSA_INVALID_ARG, "csa_argmax_rows: bad rows / V");
+  if (!x || !idx) return fail(CSA_INVALID_ARG, "csa_argmax_rows: null pointer");
+  if (!aligned(x, 4) || !aligned(idx, 8)) return fail(CSA_INVALID_ARG, "csa_argmax_rows: misaligned pointer");
   if (rows == 0) return CSA_OK;
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   hipLaunchKernelGGL(k_argmax_rows, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, idx, idx_stride, is_pad, pad_stride,
                      pad_id, maxval);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_argmax_rows: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_argmax_rows");
 }
 
 csa_status csa_argmax_rows_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
                                 uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
                                 const int32_t* t_dev, void* stream) {
-  if (rows < 0 || V < 1 || rows > 0x7fffffff || T < 1 || ys_stride < T || (pad && pad_stride < T) ||
-      (head_pad && (H < 1 || H > 0x7fffffff)))
-    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: bad rows / V / T / strides / H");
-  if (!x || !ys || !t_dev) return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: null pointer");
-  if ((((uintptr_t)x) & 3) || (((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3))
-    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_step: misaligned pointer");
-  if (rows == 0) return CSA_OK;
-  const hipStream_t st = (hipStream_t)stream;
-  const DeviceGuard guard(st);
-  hipLaunchKernelGGL(k_argmax_rows_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad, pad_stride,
-                     head_pad, (int)H, pad_id, t_dev);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_argmax_rows_step: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return argmax_step_impl("csa_argmax_rows_step", x, rows, V, ys, ys_stride, T, pad, pad_stride, head_pad, H, pad_id, false,
+                          nullptr, 0, t_dev, stream);
 }
 
 csa_status csa_argmax_rows_fin_step(const float* x, int64_t rows, int64_t V, int64_t* ys, int64_t ys_stride, int64_t T,
                                     uint8_t* pad, int64_t pad_stride, uint8_t* head_pad, int64_t H, int64_t pad_id,
                                     uint8_t* fin, int64_t eos_id, const int32_t* t_dev, void* stream) {
-  if (rows < 0 || V < 1 || rows > 0x7fffffff || T < 1 || ys_stride < T || (pad && pad_stride < T) ||
-      (head_pad && (H < 1 || H > 0x7fffffff)))
-    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: bad rows / V / T / strides / H");
-  if (!x || !ys || !fin || !t_dev) return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: null pointer");
-  if ((((uintptr_t)x) & 3) || (((uintptr_t)ys) & 7) || (((uintptr_t)t_dev) & 3))
-    return dfail(CSA_INVALID_ARG, "csa_argmax_rows_fin_step: misaligned pointer");
-  if (rows == 0) return CSA_OK;
-  const hipStream_t st = (hipStream_t)stream;
-  const DeviceGuard guard(st);
-  hipLaunchKernelGGL(k_argmax_rows_fin_step, dim3((unsigned)rows), dim3(ARG_T), 0, st, x, V, ys, ys_stride, T, pad,
-                     pad_stride, head_pad, (int)H, pad_id, fin, eos_id, t_dev);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_argmax_rows_fin_step: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return argmax_step_impl("csa_argmax_rows_fin_step", x, rows, V, ys, ys_stride, T, pad, pad_stride, head_pad, H, pad_id,
+                          true, fin, eos_id, t_dev, stream);
 }
 
 csa_status csa_decode_advance(const uint8_t* fin, int64_t rows, int64_t T, int32_t* t_dev, int32_t* state,
                               void* stream) {
-  if (rows < 0 || T < 2) return dfail(CSA_INVALID_ARG, "csa_decode_advance: bad rows / T (rows >= 0, T >= 2)");
-  if (!t_dev || !state || (rows > 0 && !fin)) return dfail(CSA_INVALID_ARG, "csa_decode_advance: null pointer");
-  if ((((uintptr_t)t_dev) & 3) || (((uintptr_t)state) & 3))
-    return dfail(CSA_INVALID_ARG, "csa_decode_advance: misaligned pointer (t_dev and state 4 bytes; fin any)");
+  if (rows < 0 || T < 2) return fail(CSA_INVALID_ARG, "csa_decode_advance: bad rows / T (rows >= 0, T >= 2)");
+  if (!t_dev || !state || (rows > 0 && !fin)) return fail(CSA_INVALID_ARG, "csa_decode_advance: null pointer");
+  if (!aligned(t_dev, 4) || !aligned(state, 4))
+    return fail(CSA_INVALID_ARG, "csa_decode_advance: misaligned pointer (t_dev and state 4 bytes; fin any)");
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   hipLaunchKernelGGL(k_decode_advance, dim3(1), dim3(ADV_T), 0, st, fin, rows, T, t_dev, state);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_decode_advance: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_decode_advance");
 }
 
 }  // extern "C"

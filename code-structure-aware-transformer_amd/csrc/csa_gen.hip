@@ -325,11 +325,6 @@ inline int reg_groups(int64_t V) {
   return per <= 6 ? (int)per : 0;
 }
 
-csa_status gfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
 bool make_gen(int64_t rows, int64_t V, float p, uint64_t seed, uint64_t offset, GenArgs* a) {
   if (rows < 0 || V < 1 || rows > 0x7fffffff || !(p >= 0.f && p < 1.f)) return false;
   a->rows = rows; a->V = V;
@@ -346,9 +341,9 @@ extern "C" {
 csa_status csa_gen_logsoftmax_fwd(const float* logits, float* logp, int64_t rows, int64_t V, float dropout,
                                   uint64_t seed, uint64_t offset, void* stream) {
   GenArgs a;
-  if (!make_gen(rows, V, dropout, seed, offset, &a)) return gfail(CSA_INVALID_ARG, "csa_gen_logsoftmax_fwd: bad rows/V/p");
+  if (!make_gen(rows, V, dropout, seed, offset, &a)) return fail(CSA_INVALID_ARG, "csa_gen_logsoftmax_fwd: bad rows/V/p");
   if (rows == 0) return CSA_OK;
-  if (!logits || !logp) return gfail(CSA_INVALID_ARG, "csa_gen_logsoftmax_fwd: null pointer");
+  if (!logits || !logp) return fail(CSA_INVALID_ARG, "csa_gen_logsoftmax_fwd: null pointer");
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   const dim3 grid((unsigned)rows);
@@ -361,20 +356,15 @@ csa_status csa_gen_logsoftmax_fwd(const float* logits, float* logp, int64_t rows
     case 6: hipLaunchKernelGGL(k_gen_fwd_r<6>, grid, dim3(RT), 0, st, logits, logp, a); break;
     default: hipLaunchKernelGGL(k_gen_fwd, grid, dim3(GT), 0, st, logits, logp, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_gen_logsoftmax_fwd: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_gen_logsoftmax_fwd");
 }
 
 csa_status csa_gen_logsoftmax_bwd(const float* dlogp, const float* logp, float* dlogits, int64_t rows, int64_t V,
                                   float dropout, uint64_t seed, uint64_t offset, void* stream) {
   GenArgs a;
-  if (!make_gen(rows, V, dropout, seed, offset, &a)) return gfail(CSA_INVALID_ARG, "csa_gen_logsoftmax_bwd: bad rows/V/p");
+  if (!make_gen(rows, V, dropout, seed, offset, &a)) return fail(CSA_INVALID_ARG, "csa_gen_logsoftmax_bwd: bad rows/V/p");
   if (rows == 0) return CSA_OK;
-  if (!dlogp || !logp || !dlogits) return gfail(CSA_INVALID_ARG, "csa_gen_logsoftmax_bwd: null pointer");
+  if (!dlogp || !logp || !dlogits) return fail(CSA_INVALID_ARG, "csa_gen_logsoftmax_bwd: null pointer");
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
   const dim3 grid((unsigned)rows);
@@ -387,12 +377,7 @@ csa_status csa_gen_logsoftmax_bwd(const float* dlogp, const float* logp, float* 
     case 6: hipLaunchKernelGGL(k_gen_bwd_r<6>, grid, dim3(RT), 0, st, dlogp, logp, dlogits, a); break;
     default: hipLaunchKernelGGL(k_gen_bwd, grid, dim3(GT), 0, st, dlogp, logp, dlogits, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_gen_logsoftmax_bwd: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_gen_logsoftmax_bwd");
 }
 
 }  // extern "C"

@@ -211,22 +211,16 @@ size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols) {
 
 csa_status csa_bias_grad(const float* dy, float* db, int64_t rows, int64_t cols, int accumulate, void* workspace,
                          void* stream) {
-  if (rows < 0 || cols < 0) {
-    csa::set_error("csa_bias_grad: negative size");
-    return CSA_INVALID_ARG;
-  }
+  if (rows < 0 || cols < 0)
+    return csa::fail(CSA_INVALID_ARG, "csa_bias_grad: negative size");
   if (cols == 0) return CSA_OK;
-  if (!db || (rows > 0 && (!dy || !workspace))) {
-    csa::set_error("csa_bias_grad: null pointer");
-    return CSA_INVALID_ARG;
-  }
+  if (!db || (rows > 0 && (!dy || !workspace)))
+    return csa::fail(CSA_INVALID_ARG, "csa_bias_grad: null pointer");
   const hipStream_t st = (hipStream_t)stream;
   const csa::DeviceGuard guard(st);
   if (rows == 0) {
-    if (!accumulate && hipMemsetAsync(db, 0, sizeof(float) * cols, st) != hipSuccess) {
-      csa::set_error("csa_bias_grad: memset failed");
-      return CSA_LAUNCH_FAILED;
-    }
+    if (!accumulate && hipMemsetAsync(db, 0, sizeof(float) * cols, st) != hipSuccess)
+      return csa::fail(CSA_LAUNCH_FAILED, "csa_bias_grad: memset failed");
     return CSA_OK;
   }
   const int rs = bg_slices(rows);
@@ -236,12 +230,7 @@ csa_status csa_bias_grad(const float* dy, float* db, int64_t rows, int64_t cols,
                      st, dy, part, rows, cols, per);
   hipLaunchKernelGGL(k_bias_grad_sum, dim3((unsigned)((cols + BS_COLS - 1) / BS_COLS)), dim3(256), 0, st, part, db, cols, rs,
                      accumulate, cols, nullptr, cols);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_bias_grad: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched("csa_bias_grad");
 }
 
 int csa_layernorm_supported(int64_t cols) { return ln_cpl(cols) > 0 ? 1 : 0; }
@@ -253,16 +242,12 @@ size_t csa_layernorm_bwd_workspace_bytes(int64_t rows, int64_t cols) {
 csa_status csa_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats,
                              int64_t rows, int64_t cols, float eps, void* stream) {
   const int cpl = ln_cpl(cols);
-  if (rows < 0 || cpl == 0) {
-    csa::set_error("csa_layernorm_fwd: cols must be a multiple of 4 in [4, 1024]");
-    return CSA_UNSUPPORTED_SHAPE;
-  }
+  if (rows < 0 || cpl == 0)
+    return csa::fail(CSA_UNSUPPORTED_SHAPE, "csa_layernorm_fwd: cols must be a multiple of 4 in [4, 1024]");
   if (rows == 0) return CSA_OK;
   if (!x || !gamma || !beta || !y || !stats || ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)gamma) |
-                                                 ((uintptr_t)beta)) & 15)) {
-    csa::set_error("csa_layernorm_fwd: null or misaligned pointer");
-    return CSA_INVALID_ARG;
-  }
+                                                 ((uintptr_t)beta)) & 15))
+    return csa::fail(CSA_INVALID_ARG, "csa_layernorm_fwd: null or misaligned pointer");
   const hipStream_t st = (hipStream_t)stream;
   const csa::DeviceGuard guard(st);
   const dim3 grid((unsigned)((rows + 3) / 4));
@@ -272,34 +257,23 @@ csa_status csa_layernorm_fwd(const float* x, const float* gamma, const float* be
     case 3: hipLaunchKernelGGL(k_ln_fwd<3>, grid, dim3(256), 0, st, x, gamma, beta, y, stats, rows, (int)cols, eps); break;
     default: hipLaunchKernelGGL(k_ln_fwd<4>, grid, dim3(256), 0, st, x, gamma, beta, y, stats, rows, (int)cols, eps);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_layernorm_fwd: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched("csa_layernorm_fwd");
 }
 
 csa_status csa_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, float* dx,
                              float* dgamma, float* dbeta, int64_t rows, int64_t cols, void* workspace, void* stream) {
   const int cpl = ln_cpl(cols);
-  if (rows < 0 || cpl == 0) {
-    csa::set_error("csa_layernorm_bwd: cols must be a multiple of 4 in [4, 1024]");
-    return CSA_UNSUPPORTED_SHAPE;
-  }
+  if (rows < 0 || cpl == 0)
+    return csa::fail(CSA_UNSUPPORTED_SHAPE, "csa_layernorm_bwd: cols must be a multiple of 4 in [4, 1024]");
   if (!dgamma || !dbeta || (rows > 0 && (!dy || !x || !stats || !gamma || !dx || !workspace)) ||
-      ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)gamma)) & 15)) {
-    csa::set_error("csa_layernorm_bwd: null or misaligned pointer");
-    return CSA_INVALID_ARG;
-  }
+      ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)gamma)) & 15))
+    return csa::fail(CSA_INVALID_ARG, "csa_layernorm_bwd: null or misaligned pointer");
   const hipStream_t st = (hipStream_t)stream;
   const csa::DeviceGuard guard(st);
   if (rows == 0) {
     if (hipMemsetAsync(dgamma, 0, sizeof(float) * cols, st) != hipSuccess ||
-        hipMemsetAsync(dbeta, 0, sizeof(float) * cols, st) != hipSuccess) {
-      csa::set_error("csa_layernorm_bwd: memset failed");
-      return CSA_LAUNCH_FAILED;
-    }
+        hipMemsetAsync(dbeta, 0, sizeof(float) * cols, st) != hipSuccess)
+      return csa::fail(CSA_LAUNCH_FAILED, "csa_layernorm_bwd: memset failed");
     return CSA_OK;
   }
   const int nwg = (int)((rows + LN_ROWS_PER_WG - 1) / LN_ROWS_PER_WG);
@@ -315,12 +289,7 @@ csa_status csa_layernorm_bwd(const float* dy, const float* x, const float* stats
   const dim3 g2((unsigned)((2 * cols + BS_COLS - 1) / BS_COLS));  // dgamma and dbeta in one launch
   hipLaunchKernelGGL(k_bias_grad_sum, g2, dim3(256), 0, st, part, dgamma, 2 * cols, nwg, 0, (int64_t)2 * cols, dbeta,
                      cols);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_layernorm_bwd: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched("csa_layernorm_bwd");
 }
 
 }  // extern "C"
@@ -411,12 +380,7 @@ static csa_status res_launch(bool bwd, const float* x, const float* o, float* y,
   const csa::DeviceGuard guard(st);
   if (bwd) hipLaunchKernelGGL(k_res_drop<true>, dim3(blocks), dim3(256), 0, st, nullptr, o, y, a);
   else hipLaunchKernelGGL(k_res_drop<false>, dim3(blocks), dim3(256), 0, st, x, o, y, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("%s: %s", name, hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched(name);
 }
 
 extern "C" {
@@ -520,12 +484,7 @@ static csa_status ffn_launch(bool bwd, const float* h, const float* dy, float* o
   const csa::DeviceGuard guard(st);
   if (bwd) hipLaunchKernelGGL(k_gelu_drop<true>, dim3(blocks), dim3(256), 0, st, h, dy, out, a);
   else hipLaunchKernelGGL(k_gelu_drop<false>, dim3(blocks), dim3(256), 0, st, h, nullptr, out, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("%s: %s", name, hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched(name);
 }
 
 extern "C" {

@@ -157,13 +157,6 @@ __global__ __launch_bounds__(64) void k_seq_metrics(const MetArgs a) {
   a.rouge[row] = rouge;
 }
 
-csa_status mfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al(const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -173,19 +166,19 @@ int csa_seq_metrics_supported(int64_t Th, int64_t Tr) {
 }
 
 csa_status csa_seq_metrics(const csa_seq_metrics_args* a, void* stream) {
-  if (!a) return mfail(CSA_INVALID_ARG, "csa_seq_metrics: null args");
+  if (!a) return fail(CSA_INVALID_ARG, "csa_seq_metrics: null args");
   if (!a->hyp || !a->ref || !a->stats || !a->bleu || !a->rouge)
-    return mfail(CSA_INVALID_ARG, "csa_seq_metrics: null pointer (hyp, ref, stats, bleu, rouge)");
+    return fail(CSA_INVALID_ARG, "csa_seq_metrics: null pointer (hyp, ref, stats, bleu, rouge)");
   if (a->rows < 0 || a->rows > 0x7fffffff || a->Th < 0 || a->Tr < 0)
-    return mfail(CSA_INVALID_ARG, "csa_seq_metrics: negative size (rows, Th, Tr) or more than 2^31 - 1 rows");
+    return fail(CSA_INVALID_ARG, "csa_seq_metrics: negative size (rows, Th, Tr) or more than 2^31 - 1 rows");
   if (a->group < 1 || a->rows % a->group != 0)
-    return mfail(CSA_INVALID_ARG, "csa_seq_metrics: group must be at least 1 and divide rows");
+    return fail(CSA_INVALID_ARG, "csa_seq_metrics: group must be at least 1 and divide rows");
   if (a->hyp_stride < a->Th || a->ref_stride < a->Tr)
-    return mfail(CSA_INVALID_ARG, "csa_seq_metrics: a row stride below Th (hyp) or Tr (ref)");
+    return fail(CSA_INVALID_ARG, "csa_seq_metrics: a row stride below Th (hyp) or Tr (ref)");
   if (!csa_seq_metrics_supported(a->Th, a->Tr))
-    return mfail(CSA_UNSUPPORTED_SHAPE, "csa_seq_metrics: Th and Tr must be in [1, 256]");
-  if (!al(a->hyp, 8) || !al(a->ref, 8) || !al(a->stats, 4) || !al(a->bleu, 8) || !al(a->rouge, 8))
-    return mfail(CSA_INVALID_ARG, "csa_seq_metrics: misaligned pointer (ids and scores 8, the int32 record 4 bytes)");
+    return fail(CSA_UNSUPPORTED_SHAPE, "csa_seq_metrics: Th and Tr must be in [1, 256]");
+  if (!aligned(a->hyp, 8) || !aligned(a->ref, 8) || !aligned(a->stats, 4) || !aligned(a->bleu, 8) || !aligned(a->rouge, 8))
+    return fail(CSA_INVALID_ARG, "csa_seq_metrics: misaligned pointer (ids and scores 8, the int32 record 4 bytes)");
   if (a->rows == 0) return CSA_OK;
   MetArgs d;
   d.hyp = a->hyp; d.hyp_s = a->hyp_stride; d.Th = (int)a->Th;
@@ -199,12 +192,7 @@ csa_status csa_seq_metrics(const csa_seq_metrics_args* a, void* stream) {
   if (T <= 64) hipLaunchKernelGGL(k_seq_metrics<1>, grid, block, 0, st, d);
   else if (T <= 128) hipLaunchKernelGGL(k_seq_metrics<2>, grid, block, 0, st, d);
   else hipLaunchKernelGGL(k_seq_metrics<4>, grid, block, 0, st, d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_seq_metrics: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_seq_metrics");
 }
 
 }  // extern "C"

@@ -78,33 +78,19 @@ __global__ __launch_bounds__(256) void k_adamw(const csa_adamw_tensor* __restric
 }  // namespace
 
 extern "C" csa_status csa_adamw_step(const csa_adamw_args* a, void* stream) {
-  if (!a) {
-    csa::set_error("csa_adamw_step: null args");
-    return CSA_INVALID_ARG;
-  }
-  if (a->ntensors < 0 || a->nchunks < 0 || a->nchunks > 0x7fffffff) {
-    csa::set_error("csa_adamw_step: bad ntensors/nchunks");
-    return CSA_INVALID_ARG;
-  }
+  if (!a) return csa::fail(CSA_INVALID_ARG, "csa_adamw_step: null args");
+  if (a->ntensors < 0 || a->nchunks < 0 || a->nchunks > 0x7fffffff)
+    return csa::fail(CSA_INVALID_ARG, "csa_adamw_step: bad ntensors/nchunks");
   if (a->nchunks == 0) return CSA_OK;
-  if (!a->tensors || !a->chunk_tensor || !a->chunk_start) {
-    csa::set_error("csa_adamw_step: null tensor table");
-    return CSA_INVALID_ARG;
-  }
-  if (!(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f)) {
-    csa::set_error("csa_adamw_step: invalid beta/eps");
-    return CSA_INVALID_ARG;
-  }
+  if (!a->tensors || !a->chunk_tensor || !a->chunk_start)
+    return csa::fail(CSA_INVALID_ARG, "csa_adamw_step: null tensor table");
+  if (!(a->beta1 >= 0.f && a->beta1 < 1.f && a->beta2 >= 0.f && a->beta2 < 1.f && a->eps >= 0.f))
+    return csa::fail(CSA_INVALID_ARG, "csa_adamw_step: invalid beta/eps");
   AdamElem c;
   c.b1 = a->beta1; c.b2 = a->beta2; c.om_b1 = a->one_minus_beta1; c.om_b2 = a->one_minus_beta2;
   c.eps = a->eps; c.neg_step = -a->step_size; c.neg_decay = -a->decay;
   const csa::DeviceGuard guard((hipStream_t)stream);
   hipLaunchKernelGGL(k_adamw, dim3((unsigned)a->nchunks), dim3(256), 0, (hipStream_t)stream, a->tensors,
                      a->chunk_tensor, a->chunk_start, c, a->grad_scale, a->found_inf);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_adamw_step: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return csa::launched("csa_adamw_step");
 }

@@ -290,32 +290,16 @@ __global__ __launch_bounds__(1024) void k_lap_pe(const LapArgs a) {
   }
 }
 
-csa_status pfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al4(const void* p) { return (((uintptr_t)p) & 3) == 0; }
-
-csa_status launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("%s: %s", what, hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
-}
-
 bool tp_fill(TpArgs& d, const char* what, const float* pos, const float* p, int64_t rows, int64_t depth, int64_t width,
              int64_t n_feat, float d_model, csa_status* st) {
   (void)what;
   *st = CSA_OK;
-  if (!pos || !p) *st = pfail(CSA_INVALID_ARG, "csa_tree_pos: null pointer (pos, p)");
-  else if (rows < 0 || depth < 1 || width < 1 || n_feat < 1) *st = pfail(CSA_INVALID_ARG, "csa_tree_pos: rows >= 0 and depth, width, n_feat >= 1");
+  if (!pos || !p) *st = fail(CSA_INVALID_ARG, "csa_tree_pos: null pointer (pos, p)");
+  else if (rows < 0 || depth < 1 || width < 1 || n_feat < 1) *st = fail(CSA_INVALID_ARG, "csa_tree_pos: rows >= 0 and depth, width, n_feat >= 1");
   else if (!csa_tree_pos_supported(depth, width, n_feat))
-    *st = pfail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos: depth <= 64 and depth * width * n_feat <= 1024");
-  else if (!(d_model > 0.f)) *st = pfail(CSA_INVALID_ARG, "csa_tree_pos: d_model must be positive");
-  else if (!al4(pos) || !al4(p)) *st = pfail(CSA_INVALID_ARG, "csa_tree_pos: misaligned pointer");
+    *st = fail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos: depth <= 64 and depth * width * n_feat <= 1024");
+  else if (!(d_model > 0.f)) *st = fail(CSA_INVALID_ARG, "csa_tree_pos: d_model must be positive");
+  else if (!aligned(pos, 4) || !aligned(p, 4)) *st = fail(CSA_INVALID_ARG, "csa_tree_pos: misaligned pointer");
   if (*st != CSA_OK) return false;
   d.pos = pos; d.p = p; d.g = nullptr; d.out = nullptr; d.ws = nullptr; d.dp = nullptr;
   d.rows = rows; d.depth = (int)depth; d.width = (int)width; d.F = (int)n_feat; d.nblk = 0; d.d_model = d_model;
@@ -342,10 +326,10 @@ csa_status csa_tree_pos_fwd(const float* pos, const float* p, float* out, int64_
   TpArgs d;
   csa_status s;
   if (!tp_fill(d, "csa_tree_pos_fwd", pos, p, rows, depth, width, n_feat, d_model, &s)) return s;
-  if (!out || !al4(out)) return pfail(CSA_INVALID_ARG, "csa_tree_pos_fwd: null or misaligned out");
+  if (!out || !aligned(out, 4)) return fail(CSA_INVALID_ARG, "csa_tree_pos_fwd: null or misaligned out");
   if (rows == 0) return CSA_OK;
   const int64_t nblk = (rows + TP_FWD_ROWS - 1) / TP_FWD_ROWS;
-  if (nblk > 0x7fffffff) return pfail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos_fwd: too many rows");
+  if (nblk > 0x7fffffff) return fail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos_fwd: too many rows");
   d.out = out;
   const hipStream_t st = (hipStream_t)stream;
   const DeviceGuard guard(st);
@@ -358,11 +342,11 @@ csa_status csa_tree_pos_bwd(const float* pos, const float* p, const float* dout,
   TpArgs d;
   csa_status s;
   if (!tp_fill(d, "csa_tree_pos_bwd", pos, p, rows, depth, width, n_feat, d_model, &s)) return s;
-  if (!dp || !al4(dp)) return pfail(CSA_INVALID_ARG, "csa_tree_pos_bwd: null or misaligned dp");
-  if (rows > 0 && (!dout || !al4(dout) || !workspace || (((uintptr_t)workspace) & 7)))
-    return pfail(CSA_INVALID_ARG, "csa_tree_pos_bwd: null or misaligned dout / workspace");
+  if (!dp || !aligned(dp, 4)) return fail(CSA_INVALID_ARG, "csa_tree_pos_bwd: null or misaligned dp");
+  if (rows > 0 && (!dout || !aligned(dout, 4) || !workspace || !aligned(workspace, 8)))
+    return fail(CSA_INVALID_ARG, "csa_tree_pos_bwd: null or misaligned dout / workspace");
   const int64_t nblk = (rows + TP_BWD_ROWS - 1) / TP_BWD_ROWS;
-  if (nblk > 0x7fffffff) return pfail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos_bwd: too many rows");
+  if (nblk > 0x7fffffff) return fail(CSA_UNSUPPORTED_SHAPE, "csa_tree_pos_bwd: too many rows");
   d.g = dout; d.dp = dp; d.ws = (double*)workspace; d.nblk = (int)nblk;
   const int CF = d.depth * d.width * d.F;
   const hipStream_t st = (hipStream_t)stream;
@@ -383,16 +367,17 @@ int csa_lap_pe_supported(int64_t N, int64_t pegen_dim) {
 }
 
 csa_status csa_lap_pe(const csa_lap_pe_args* a, void* stream) {
-  if (!a) return pfail(CSA_INVALID_ARG, "csa_lap_pe: null args");
+  if (!a) return fail(CSA_INVALID_ARG, "csa_lap_pe: null args");
   if (a->B < 0 || a->B > 0x7fffffff || a->N < 1 || a->pegen_dim < 1)
-    return pfail(CSA_INVALID_ARG, "csa_lap_pe: B >= 0 and N, pegen_dim >= 1");
+    return fail(CSA_INVALID_ARG, "csa_lap_pe: B >= 0 and N, pegen_dim >= 1");
   if (!csa_lap_pe_supported(a->N, a->pegen_dim))
-    return pfail(CSA_UNSUPPORTED_SHAPE, "csa_lap_pe: needs N <= pegen_dim and an N x N fp32 matrix within the CU's LDS");
+    return fail(CSA_UNSUPPORTED_SHAPE, "csa_lap_pe: needs N <= pegen_dim and an N x N fp32 matrix within the CU's LDS");
   if (a->B == 0) return CSA_OK;
   if (!a->adj || !a->num_node || !a->pe || !a->eigenvalues || !a->status)
-    return pfail(CSA_INVALID_ARG, "csa_lap_pe: null pointer (adj, num_node, pe, eigenvalues, status)");
-  if (!al4(a->num_node) || !al4(a->pe) || !al4(a->eigenvalues) || !al4(a->status) || !al4(a->sweeps))
-    return pfail(CSA_INVALID_ARG, "csa_lap_pe: misaligned pointer");
+    return fail(CSA_INVALID_ARG, "csa_lap_pe: null pointer (adj, num_node, pe, eigenvalues, status)");
+  if (!aligned(a->num_node, 4) || !aligned(a->pe, 4) || !aligned(a->eigenvalues, 4) || !aligned(a->status, 4) ||
+      !aligned(a->sweeps, 4))
+    return fail(CSA_INVALID_ARG, "csa_lap_pe: misaligned pointer");
   LapArgs d;
   d.adj = a->adj; d.num_node = a->num_node; d.pe = a->pe; d.eval = a->eigenvalues; d.status = a->status;
   d.sweeps = a->sweeps; d.N = (int)a->N; d.P = (int)a->pegen_dim;

@@ -27,6 +27,7 @@
 //                  class. Entries off the prefix cost a load and a compare, so the deeper passes are cheap;
 //   draw           sum exp over the kept set and the noisy arg-max.
 #include "csa_common.hpp"
+#include "csa_row_select.hpp"
 #include "../../include/csa_hip.h"
 
 #include <math.h>
@@ -39,7 +40,6 @@ constexpr int SAMPLE_THREADS = 256;
 constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
 constexpr int SAMPLE_MAX_V = 32768;
 constexpr uint32_t RNG_SAMPLE = 7u;
-constexpr int NO_IDX = 0x7fffffff;  // "no entry": loses every tie against a real index
 
 struct SampArgs {
   const float* z; int64_t z_s; int V;
@@ -61,16 +61,6 @@ __device__ __forceinline__ bool is_cand(float y) { return y > -INFINITY; }  // n
 __device__ __forceinline__ uint32_t okey(float y) {
   const uint32_t u = __float_as_uint(y + 0.f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ bool ahead(float v, int i, float vo, int io) { return v > vo || (v == vo && i < io); }
-
-__device__ __forceinline__ void lse_merge(float& m, float& s, float mo, float so) {
-  const float mn = fmaxf(m, mo);
-  const float a = (m > -INFINITY) ? s * expf(m - mn) : 0.f;
-  const float b = (mo > -INFINITY) ? so * expf(mo - mn) : 0.f;
-  m = mn;
-  s = a + b;
 }
 
 // u = ((w >> 9) + 0.5) 2^-23 in (0, 1), exact in fp32; g = -log(-log u)
@@ -367,13 +357,6 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_rows(const SampArgs a
   }
 }
 
-csa_status sfail(csa_status s, const char* m) {
-  csa::set_error("%s", m);
-  return s;
-}
-
-inline bool al(const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -381,21 +364,22 @@ extern "C" {
 int csa_sample_rows_supported(int64_t V) { return (V >= 1 && V <= SAMPLE_MAX_V) ? 1 : 0; }
 
 csa_status csa_sample_rows(const csa_sample_rows_args* a, void* stream) {
-  if (!a) return sfail(CSA_INVALID_ARG, "csa_sample_rows: null args");
-  if (!csa_sample_rows_supported(a->V)) return sfail(CSA_UNSUPPORTED_SHAPE, "csa_sample_rows: V must be in [1, 32768]");
+  if (!a) return fail(CSA_INVALID_ARG, "csa_sample_rows: null args");
+  if (!csa_sample_rows_supported(a->V)) return fail(CSA_UNSUPPORTED_SHAPE, "csa_sample_rows: V must be in [1, 32768]");
   if (a->rows < 0 || a->rows > 0x7fffffff || a->T < 2 || a->T > 0x7fffffff)
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: bad rows or T (T >= 2)");
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: bad rows or T (T >= 2)");
   if (!(a->inv_temperature > 0.f) || !(a->inv_temperature < INFINITY))
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: the temperature must be positive (inv_temperature in (0, inf))");
-  if (!(a->top_p > 0.f)) return sfail(CSA_INVALID_ARG, "csa_sample_rows: top_p must be positive (>= 1 turns it off)");
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: the temperature must be positive (inv_temperature in (0, inf))");
+  if (!(a->top_p > 0.f)) return fail(CSA_INVALID_ARG, "csa_sample_rows: top_p must be positive (>= 1 turns it off)");
   if (a->top_k < 0 || a->top_k > 0x7fffffff)
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: top_k must not be negative (0 turns it off)");
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: top_k must not be negative (0 turns it off)");
   if (a->logits_stride < a->V || a->ys_stride < a->T || a->pad_stride < a->T || (a->logp && a->logp_stride < a->T - 1))
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: a row stride below V (logits), T (ys, pad) or T - 1 (logp)");
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: a row stride below V (logits), T (ys, pad) or T - 1 (logp)");
   if (!a->logits || !a->ys || !a->pad || !a->fin || !a->rng_dev || !a->t_dev)
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: null pointer");
-  if (!al(a->logits, 4) || !al(a->ys, 8) || !al(a->logp, 4) || !al(a->rng_dev, 8) || !al(a->t_dev, 4))
-    return sfail(CSA_INVALID_ARG, "csa_sample_rows: misaligned pointer (tokens and rng 8, the fp32 / int32 arrays 4 bytes)");
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: null pointer");
+  if (!aligned(a->logits, 4) || !aligned(a->ys, 8) || !aligned(a->logp, 4) || !aligned(a->rng_dev, 8) ||
+      !aligned(a->t_dev, 4))
+    return fail(CSA_INVALID_ARG, "csa_sample_rows: misaligned pointer (tokens and rng 8, the fp32 / int32 arrays 4 bytes)");
   if (a->rows == 0) return CSA_OK;
   SampArgs d;
   d.z = a->logits; d.z_s = a->logits_stride; d.V = (int)a->V;
@@ -415,12 +399,7 @@ csa_status csa_sample_rows(const csa_sample_rows_args* a, void* stream) {
     hipLaunchKernelGGL(k_sample_rows<true>, dim3((unsigned)a->rows), dim3(SAMPLE_THREADS), 0, st, d);
   else
     hipLaunchKernelGGL(k_sample_rows<false>, dim3((unsigned)a->rows), dim3(SAMPLE_THREADS), 0, st, d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    csa::set_error("csa_sample_rows: %s", hipGetErrorString(e));
-    return CSA_LAUNCH_FAILED;
-  }
-  return CSA_OK;
+  return launched("csa_sample_rows");
 }
 
 }  // extern "C"

@@ -3593,11 +3593,6 @@ struct Stage {  // records caller-owned events around one stage (no-op when prof
   }
 };
 
-csa_status fail(csa_status s, const char* msg) {
-  csa::set_error("%s", msg);
-  return s;
-}
-
 // a HIP runtime call (not a launch) failed: report the thread's last HIP error
 csa_status fail_hip(const char* what) {
   const hipError_t e = hipGetLastError();

@@ -1,4 +1,4 @@
-"""Oracle of the decoding constraints (csa_amd.decode_ops.constrain_rows, csa_amd.model.DecodingConstraints), test
+"""Oracle of the decoding constraints (csa_amd.decode_ops.constrain_rows, csa_amd.decoding.DecodingConstraints), test
 infrastructure only.
 
 constrain_np restates the rule of include/csa_hip.h (csa_constrain_rows) as plain Python loops over the rows and the

@@ -1,4 +1,4 @@
-"""Oracles and cases of the early stop at EOS (csa_amd.model._SteppedDecoding, decode_ops.decode_advance and the
+"""Oracles and cases of the early stop at EOS (csa_amd.decoding._SteppedDecoding, decode_ops.decode_advance and the
 finished-flag form of argmax_rows), test infrastructure only.
 
 steps_rule restates the stopping rule on an oracle's record of finished flags; greedy_eos_ref is the uncached greedy

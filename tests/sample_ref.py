@@ -1,4 +1,4 @@
-"""Oracle of sampled decoding (csa_amd.decode_ops.sample_rows, csa_amd.model.SamplingGenerator), test infrastructure only.
+"""Oracle of sampled decoding (csa_amd.decode_ops.sample_rows, csa_amd.decoding.SamplingGenerator), test infrastructure only.
 
 sample_rows_np restates the rule of include/csa_hip.h (csa_sample_rows) in fp64 on top of oracle/philox.py: the
 temperature product alone is formed in fp32, as specified; the sets, the softmax masses, the Gumbel noise and the noisy

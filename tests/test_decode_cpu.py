@@ -180,3 +180,8 @@ def test_decode_attn_supported_head_dims():
 def test_cached_generator_is_exported_beside_the_plain_one():
     from csa_amd.model import CachedGreedyGenerator, GreedyGenerator
     assert issubclass(CachedGreedyGenerator, GreedyGenerator)
+    import csa_amd.decoding
+    import csa_amd.model
+    for name in ("DecodingConstraints", "_SteppedDecoding", "CachedGreedyGenerator", "BeamSearchGenerator",
+                 "SamplingGenerator"):
+        assert getattr(csa_amd.model, name) is getattr(csa_amd.decoding, name), name

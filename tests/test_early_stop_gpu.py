@@ -254,7 +254,7 @@ def test_a_parked_step_stores_nothing(kind):
     m, enc, src_mask = _case(_NAME[kind])
     with torch.no_grad():
         cache = m.decoder.make_cache(enc, src_mask, T, **gen._cache_options)
-        e = gen._state(cache, False) if kind == "greedy" else gen._state(cache, True) if kind == "sampling" else gen._state(cache)
+        e = gen._state(cache, return_logp=kind == "sampling")
         gen._reset(e)
         if kind == "sampling":
             e.rng.copy_(torch.tensor([ref.SAMPLING_SEED, 0]))
