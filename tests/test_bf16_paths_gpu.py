@@ -242,12 +242,16 @@ def _weights(params):
             [params[f"proj.{i}.bias"].cuda() for i in (0, 3, 6)])
 
 
-def run_sbm_gpu(c, bf16=True, maps=True, schedule=CSA_SCHED_IN_ORDER, zero_maps=False):
+def run_sbm_gpu(c, bf16=True, maps=True, schedule=CSA_SCHED_IN_ORDER, zero_maps=False, uniforms=None):
+    """uniforms: host (B, H, N, M) draws handed to the forward whatever the mode (train mode with them is the
+    HAS_U && DROP instantiation of k_attn_fwd); None: the case's own in eval mode, the kernel's Philox draws in train."""
     kw = c["kw"]
     k = kw["num_clusters"]
     cw, pw, pb = _weights(kw["params"])
     q, kk, v, mk = (kw[n].float().contiguous().cuda() for n in ("Q", "K", "V", "mask"))
     uu = None if c["train"] else kw["u"].float().cuda()
+    if uniforms is not None:
+        uu = uniforms.float().cuda()
     X, sp, state = torch.ops.csa.sbm_fwd(q, kk, v, mk, cw, pw, pb, uu, k, SEED, OFFSET, c["attn_p"], c["proj_p"],
                                          False, bf16, False)
     graph, _ = torch.ops.csa.sbm_maps(q, kk, v, mk, state, k, False)

@@ -135,8 +135,9 @@ def rect_tol(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------
 def check_graph_fp32(c, graph, expA):
     """The GPU's graph equals the oracle's own sampling on its fp64 expA except at fp32 ties (eval: a host uniform
-    within 1e-6 of clamp(expA); train: a 16-bit draw within 0.5 of clamp(expA) 65536), in fewer than 1e-4 of the draws."""
-    if c["train"]:
+    within 1e-6 of clamp(expA); train: a 16-bit draw within 0.5 of clamp(expA) 65536), in fewer than 1e-4 of the draws.
+    A train-mode case that carries host_uniforms (the forward was handed kw["u"]) obeys the eval rule."""
+    if c["train"] and not c.get("host_uniforms"):
         want = philox.ste_graph(expA.numpy(), c["u16"])
         thr = np.clip(expA.numpy(), 0.01, 0.99) * 65536.0
         diff = want != graph.numpy().astype(bool)
