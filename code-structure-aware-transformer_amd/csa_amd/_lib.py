@@ -128,6 +128,14 @@ class AdamwArgs(ctypes.Structure):
 ADAMW_CHUNK = 4096  # CSA_ADAMW_CHUNK
 
 
+class GradSumsqArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("tensors", vp), ("chunk_tensor", vp), ("chunk_start", vp),
+        ("ntensors", i64), ("nchunks", i64),
+        ("partials", vp), ("first", i64),
+    ]
+
+
 class DecodeAttnArgs(ctypes.Structure):  # ABI v10
     _fields_ = [
         ("B", i64), ("H", i64), ("hd", i64), ("len", i64), ("t", i64),
@@ -282,6 +290,12 @@ def lib():
     L.csa_collate_relations.argtypes = [vp, vp, i64, vp, vp, vp, vp, ctypes.c_int]
     L.csa_adamw_step.restype = ctypes.c_int
     L.csa_adamw_step.argtypes = [ctypes.POINTER(AdamwArgs), vp]
+    L.csa_grad_sumsq.restype = ctypes.c_int  # v10 additions: global gradient-norm clipping
+    L.csa_grad_sumsq.argtypes = [ctypes.POINTER(GradSumsqArgs), vp]
+    L.csa_grad_norm_finish.restype = ctypes.c_int
+    L.csa_grad_norm_finish.argtypes = [vp, i64, vp, f32, vp, vp]
+    L.csa_adamw_step_clipped.restype = ctypes.c_int
+    L.csa_adamw_step_clipped.argtypes = [ctypes.POINTER(AdamwArgs), vp, vp]
     L.csa_decode_attn_supported.restype = ctypes.c_int
     L.csa_decode_attn_supported.argtypes = [i64]
     L.csa_decode_attn.restype = ctypes.c_int
@@ -352,7 +366,7 @@ EXPORTED_SYMBOLS = (
     "csa_sbm_bwd_workspace_bytes", "csa_sbm_fwd", "csa_sbm_maps", "csa_sbm_bwd", "csa_dense_attn_fwd",
     "csa_dense_attn_bwd", "csa_ste_sample",
     "csa_ste_backward", "csa_rel_attn_state_bytes", "csa_rel_attn_bwd_workspace_bytes", "csa_rel_attn_fwd", "csa_rel_attn_bwd",
-    "csa_adamw_step", "csa_gen_logsoftmax_fwd", "csa_gen_logsoftmax_bwd",
+    "csa_adamw_step", "csa_grad_sumsq", "csa_grad_norm_finish", "csa_adamw_step_clipped", "csa_gen_logsoftmax_fwd", "csa_gen_logsoftmax_bwd",
     "csa_bias_grad_workspace_bytes", "csa_bias_grad", "csa_ast_relations",
     "csa_layernorm_supported", "csa_layernorm_bwd_workspace_bytes", "csa_layernorm_fwd", "csa_layernorm_bwd",
     "csa_residual_dropout_fwd", "csa_residual_dropout_bwd", "csa_gelu_dropout_fwd", "csa_gelu_dropout_bwd",

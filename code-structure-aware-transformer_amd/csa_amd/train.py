@@ -24,6 +24,85 @@ import torch
 import torch.distributed as dist
 
 
+def _chunk_maps(sizes):
+    """Host tables of csa_adamw_step / csa_grad_sumsq for tensors of `sizes` elements: the tensor of every
+    CSA_ADAMW_CHUNK-element chunk (int32), the first chunk of every tensor (int64), the chunk count."""
+    from ._lib import ADAMW_CHUNK
+    nchunk = [(n + ADAMW_CHUNK - 1) // ADAMW_CHUNK for n in sizes]
+    start = torch.zeros(len(sizes), dtype=torch.int64)
+    if len(sizes) > 1:
+        start[1:] = torch.cumsum(torch.tensor(nchunk[:-1], dtype=torch.int64), 0)
+    owner = torch.repeat_interleave(torch.arange(len(sizes), dtype=torch.int32),
+                                    torch.tensor(nchunk, dtype=torch.int64))
+    return owner, start, sum(nchunk)
+
+
+def _grad_sumsq(tables, partials, first, stream):
+    """One csa_grad_sumsq launch over a group's (desc, owner, start, ntensors, nchunks) tables."""
+    from ._lib import GradSumsqArgs, check, lib, on_device
+    desc, owner, start, nt, nc = tables
+    a = GradSumsqArgs(tensors=desc.data_ptr(), chunk_tensor=owner.data_ptr(), chunk_start=start.data_ptr(),
+                      ntensors=nt, nchunks=nc, partials=partials.data_ptr(), first=first)
+    with on_device(partials.device):
+        check(lib().csa_grad_sumsq(ctypes.byref(a), stream), "csa_grad_sumsq")
+
+
+def _grad_norm_finish(partials, n, grad_scale, max_norm, state, stream):
+    from ._lib import check, lib, on_device
+    scale = None if grad_scale is None else grad_scale.data_ptr()
+    with on_device(state.device):
+        check(lib().csa_grad_norm_finish(partials.data_ptr(), n, scale, max_norm, state.data_ptr(), stream),
+              "csa_grad_norm_finish")
+
+
+def _host_norm_state(grads, grad_scale, max_norm):
+    """The 4-float state of csa_grad_norm_finish for host gradients, with torch ops: fp64 sum of squares,
+    the norm of the unscaled gradients in fp32, clip_grad_norm_'s coefficient, the non-finite flag."""
+    total = torch.zeros((), dtype=torch.float64)
+    for g in grads:
+        total += g.detach().double().square().sum()
+    inv = 1.0 if grad_scale is None else 1.0 / grad_scale.double().cpu()
+    norm = (total.sqrt() * inv).float()
+    coef = torch.ones(()) if max_norm <= 0.0 or not grads else (max_norm / (norm + 1e-6)).clamp(max=1.0)
+    bad = not bool(torch.isfinite(norm))
+    return torch.stack([norm.reshape(()), torch.zeros(()) if bad else coef.reshape(()),
+                        torch.tensor(float(bad)), torch.zeros(())])
+
+
+def grad_norm(parameters, grad_scale=None):
+    """Global L2 norm of the parameters' gradients as a 0-dim fp32 tensor on their device, without a host sync:
+    the two kernels of AdamW(max_grad_norm=...) (csa_grad_sumsq, csa_grad_norm_finish: fp64 sums in a fixed
+    order), for logging in runs that do not clip. grad_scale: the GradScaler's scale as a tensor (the norm
+    is then that of the unscaled gradients). Gradients must be contiguous fp32 on one device; parameters
+    without a gradient are left out (none at all: 0). Host gradients take torch ops. Each call builds and
+    sends its own chunk tables; the optimizer's clipping path reuses its cached ones instead."""
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.zeros(())
+    dev = grads[0].device
+    if any(g.device != dev for g in grads):
+        raise RuntimeError("grad_norm: all gradients must be on one device")
+    if dev.type != "cuda":
+        return _host_norm_state(grads, grad_scale, 0.0)[0]
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise RuntimeError("grad_norm: gradients must be contiguous fp32")
+    if grad_scale is not None:
+        grad_scale = grad_scale.to(device=dev, dtype=torch.float32).contiguous()
+    sizes = tuple(g.numel() for g in grads)
+    owner, start, nchunks = _chunk_maps(sizes)
+    # csa_adamw_tensor descriptors: only grad and numel are read
+    host = torch.tensor([x for g, n in zip(grads, sizes) for x in (0, g.data_ptr(), 0, 0, n)],
+                        dtype=torch.int64).pin_memory()
+    tables = (host.to(dev, non_blocking=True), owner.to(dev), start.to(dev), len(grads), nchunks)
+    partials = torch.empty(max(nchunks, 1), dtype=torch.float64, device=dev)
+    state = torch.empty(4, dtype=torch.float32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _grad_sumsq(tables, partials, 0, stream)
+    _grad_norm_finish(partials, nchunks, grad_scale, 0.0, state, stream)
+    return state[0]
+
+
 class AdamW(torch.optim.Optimizer):
     """script/optimizer.py:10-106 (decoupled weight decay, optional bias correction): one csa_adamw_step
     launch for all CUDA parameters, foreach ops on CPU.
@@ -33,16 +112,39 @@ class AdamW(torch.optim.Optimizer):
     on inf/NaN itself, so `scaler.step()` needs no host sync. The skip then happens on the device
     while the host-side step counter still advances; bias correction depends on that counter, so
     groups with correct_bias=True (not the reference's configuration, script/train.py:80) take the
-    host-synchronised skip instead."""
+    host-synchronised skip instead.
+
+    max_grad_norm (the reference constructs its trainer with 1.0, script/train.py:93,171): clip the
+    gradients of ALL parameter groups by their global L2 norm inside step(), with torch's
+    clip_grad_norm_ coefficient min(1, max_norm / (norm + 1e-6)). On GPU that is one csa_grad_sumsq
+    launch per parameter group and one csa_grad_norm_finish in front of the update launches: fp64
+    sums in a fixed order, no atomics, no host sync. The norm is that of the UNSCALED gradients under a
+    GradScaler, and the update uses each gradient as (g / scale) * coef (unscale_, then
+    clip_grad_norm_); `p.grad` itself is never written. After step(), `last_grad_norm` and
+    `last_clip_coef` are 0-dim views (on the parameters' device) of the state the next step overwrites;
+    reading them is the caller's sync. A non-finite norm SKIPS the step like found_inf does
+    (last_clip_coef 0) where torch would write NaN into every parameter; groups with correct_bias=True
+    decide that skip on the host. A step that found_inf skips on the host returns before the norm is
+    taken. None (default): no clipping, no extra launch or allocation, the same bits as ever. All
+    gradients must live on one device. Data parallel: step() runs after the gradient all-reduce, so every
+    rank computes the same norm, bit for bit, from the same averaged gradients; no collective is added."""
 
     _step_supports_amp_scaling = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
+                 max_grad_norm=None):
         if lr < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or eps < 0.0:
             raise ValueError("invalid AdamW hyper-parameters")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (0.0 < max_grad_norm < float("inf")):
+                raise ValueError("AdamW: max_grad_norm must be a positive finite number or None")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       correct_bias=correct_bias))
         self._tables = {}  # param-group index -> device chunk tables + descriptors for csa_adamw_step
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm = self.last_clip_coef = None
+        self._clip_partials = self._clip_state = None  # fp64 per-chunk sums, 4-float state (clipping only)
 
     def _chunk_tables(self, key, ps, grads, m, v):
         """Device tables for csa_adamw_step, cached per parameter group (`key`): chunk -> tensor and
@@ -50,18 +152,12 @@ class AdamW(torch.optim.Optimizer):
         exp_avg, exp_avg_sq, numel) descriptors, re-sent only when a pointer changes (set_to_none grads
         may come back elsewhere) through a pinned non-blocking copy, so the step never waits for the
         device. Each group keeps its own entry, so a decay/no-decay split does not rebuild per step."""
-        from ._lib import ADAMW_CHUNK
         dev = ps[0].device
         sizes = tuple(p.numel() for p in ps)
         ent = self._tables.get(key)
         if ent is None or ent["sizes"] != sizes:
-            nchunk = [(n + ADAMW_CHUNK - 1) // ADAMW_CHUNK for n in sizes]
-            start = torch.zeros(len(sizes), dtype=torch.int64)
-            if len(sizes) > 1:
-                start[1:] = torch.cumsum(torch.tensor(nchunk[:-1], dtype=torch.int64), 0)
-            owner = torch.repeat_interleave(torch.arange(len(sizes), dtype=torch.int32),
-                                            torch.tensor(nchunk, dtype=torch.int64))
-            ent = {"sizes": sizes, "owner": owner.to(dev), "start": start.to(dev), "nchunks": sum(nchunk),
+            owner, start, nchunks = _chunk_maps(sizes)
+            ent = {"sizes": sizes, "owner": owner.to(dev), "start": start.to(dev), "nchunks": nchunks,
                    "ptrs": None, "desc": None}
             self._tables[key] = ent
         ptrs = tuple(x for q in zip(ps, grads, m, v) for x in (q[0].data_ptr(), q[1].data_ptr(),
@@ -72,12 +168,49 @@ class AdamW(torch.optim.Optimizer):
             ent["desc"], ent["ptrs"] = host.to(dev, non_blocking=True), ptrs
         return ent["desc"], ent["owner"], ent["start"], len(ps), ent["nchunks"]
 
-    def _fused_step(self, gi, group, ps, grads, m, v, step_size, grad_scale=None, found_inf=None):
-        from ._lib import AdamwArgs, check, lib, on_device
-        for t in ps + grads + m + v:
+    @staticmethod
+    def _check_fp32(tensors):
+        for t in tensors:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("csa_adamw_step: parameters, grads and state must be contiguous fp32")
-        desc, owner, start, nt, nc = self._chunk_tables(gi, ps, grads, m, v)
+
+    def _measure_norm(self, work, grad_scale):
+        """The global gradient norm over every group of `work` -> (4-float state {norm, coef, non-finite, 0}
+        on the gradients' device, {group index: chunk tables}). GPU: one csa_grad_sumsq per group over the
+        group's cached tables into one cached fp64 partials tensor, then one csa_grad_norm_finish."""
+        all_grads = [g for w in work for g in w[3]]
+        dev = all_grads[0].device
+        if any(g.device != dev for g in all_grads):
+            raise RuntimeError("AdamW(max_grad_norm=...): all gradients must be on one device")
+        tabs = {}
+        if dev.type != "cuda":
+            state = _host_norm_state(all_grads, grad_scale, self.max_grad_norm)
+        else:
+            for gi, _, ps, grads, m, v in work:
+                self._check_fp32(ps + grads + m + v)
+                tabs[gi] = self._chunk_tables(gi, ps, grads, m, v)
+            total = sum(t[4] for t in tabs.values())
+            if self._clip_partials is None or self._clip_partials.device != dev or self._clip_partials.numel() < total:
+                self._clip_partials = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+            if self._clip_state is None or self._clip_state.device != dev:
+                self._clip_state = torch.empty(4, dtype=torch.float32, device=dev)
+            state = self._clip_state
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            first = 0
+            for t in tabs.values():
+                _grad_sumsq(t, self._clip_partials, first, stream)
+                first += t[4]
+            _grad_norm_finish(self._clip_partials, total, grad_scale, self.max_grad_norm, state, stream)
+        self.last_grad_norm, self.last_clip_coef = state[0], state[1]
+        return state, tabs
+
+    def _fused_step(self, gi, group, ps, grads, m, v, step_size, grad_scale=None, found_inf=None, tables=None,
+                    clip=None):
+        from ._lib import AdamwArgs, check, lib, on_device
+        if tables is None:
+            self._check_fp32(ps + grads + m + v)
+            tables = self._chunk_tables(gi, ps, grads, m, v)
+        desc, owner, start, nt, nc = tables
         b1, b2 = group["betas"]
         a = AdamwArgs(tensors=desc.data_ptr(), chunk_tensor=owner.data_ptr(), chunk_start=start.data_ptr(),
                       ntensors=nt, nchunks=nc, beta1=b1, beta2=b2, one_minus_beta1=1.0 - b1,
@@ -86,8 +219,9 @@ class AdamW(torch.optim.Optimizer):
                       grad_scale=None if grad_scale is None else grad_scale.data_ptr(),
                       found_inf=None if found_inf is None else found_inf.data_ptr())
         stream = ctypes.c_void_p(torch.cuda.current_stream(ps[0].device).cuda_stream)
+        clip = None if clip is None else clip.data_ptr()  # NULL: csa_adamw_step itself, the unclipped kernel
         with on_device(ps[0].device):
-            check(lib().csa_adamw_step(ctypes.byref(a), stream), "csa_adamw_step")
+            check(lib().csa_adamw_step_clipped(ctypes.byref(a), clip, stream), "csa_adamw_step")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -101,11 +235,11 @@ class AdamW(torch.optim.Optimizer):
             on_host = any(p.grad is not None and not p.is_cuda for g in self.param_groups for p in g["params"])
             if (on_host or any(g["correct_bias"] for g in self.param_groups)) and found_inf.item() != 0.0:
                 return loss  # GradScaler skip, decided on the host (no state change)
+        work = []  # (group index, group, params with a gradient, their grads, exp_avg, exp_avg_sq)
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
-            grads = [p.grad for p in ps]
             m, v = [], []
             for p in ps:
                 st = self.state[p]
@@ -113,19 +247,31 @@ class AdamW(torch.optim.Optimizer):
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p)
                     st["exp_avg_sq"] = torch.zeros_like(p)
-                st["step"] += 1
                 m.append(st["exp_avg"])
                 v.append(st["exp_avg_sq"])
+            work.append((gi, group, ps, [p.grad for p in ps], m, v))
+        clip, tabs = None, {}
+        if self.max_grad_norm is not None and work:
+            clip, tabs = self._measure_norm(work, grad_scale)
+            # the skip on a non-finite norm: on the device (k_adamw reads clip[2]) unless the host's step counter
+            # must not advance (bias correction) or the parameters live on the host
+            if (not clip.is_cuda or any(w[1]["correct_bias"] for w in work)) and clip[2].item() != 0.0:
+                return loss
+        for gi, group, ps, grads, m, v in work:
+            for p in ps:
+                self.state[p]["step"] += 1
             b1, b2 = group["betas"]
             step_size = group["lr"]
             if group["correct_bias"]:
                 t = self.state[ps[0]]["step"]
                 step_size = step_size * (1.0 - b2 ** t) ** 0.5 / (1.0 - b1 ** t)
             if ps[0].is_cuda:
-                self._fused_step(gi, group, ps, grads, m, v, step_size, grad_scale, found_inf)
+                self._fused_step(gi, group, ps, grads, m, v, step_size, grad_scale, found_inf, tabs.get(gi), clip)
                 continue
             if grad_scale is not None:
                 grads = torch._foreach_mul(grads, (1.0 / grad_scale.double()).float().item())
+            if clip is not None:
+                grads = torch._foreach_mul(grads, clip[1].item())
             torch._foreach_mul_(m, b1)
             torch._foreach_add_(m, grads, alpha=1.0 - b1)
             torch._foreach_mul_(v, b2)

@@ -12,6 +12,8 @@
  *   csa_rel_attn_fwd   module/disentangled_attn.py:44-65 DisentangledAttn.rel_attn
  *   csa_rel_attn_bwd   autograd of rel_attn (gather backward = deterministic scatter-add)
  *   csa_adamw_step     script/optimizer.py:49-106 AdamW.step (all parameters in one launch)
+ *   csa_grad_sumsq / csa_grad_norm_finish / csa_adamw_step_clipped  global gradient-norm clipping in front of
+ *                      that step (script/train.py:93,171 construct the trainer with max_grad_norm=1.0)
  *   csa_gen_logsoftmax_fwd/_bwd  module/components.py:95-102 Generator: log(softmax(dropout(logits)))
  *   csa_bias_grad      Linear bias gradient (column sums of dY) of the encoder/decoder glue
  *   csa_layernorm_fwd/_bwd  nn.LayerNorm of the encoder glue (module/components.py SublayerConnection)
@@ -265,6 +267,38 @@ typedef struct csa_adamw_args {
 } csa_adamw_args;
 
 csa_status csa_adamw_step(const csa_adamw_args* a, void* stream);
+
+/* ---- v10 addition: global gradient-norm clipping in front of the AdamW step, no host sync ----
+ * The L2 norm over every gradient of the step, in two launches driven by the AdamW tables (no atomics,
+ * a fixed summation order: the result is a pure function of the gradients):
+ *   csa_grad_sumsq: one workgroup per chunk writes partials[first + chunk] = sum of g^2 over the chunk,
+ *     the raw gradients squared and accumulated in fp64 (1e25-sized or GradScaler-scaled gradients do
+ *     not overflow). Only the descriptors' grad and numel are read. Parameter groups with tables of
+ *     their own fill disjoint ranges of one partials array through `first`. nchunks == 0: CSA_OK, no launch.
+ *   csa_grad_norm_finish: one workgroup sums the n partials and writes the 4-float state
+ *     state[0] = (float)(sqrt(total) / (double)*grad_scale)   the norm of the UNSCALED gradients
+ *                                                            (grad_scale NULL: scale 1)
+ *     state[1] = min(1, max_norm / (state[0] + 1e-6))        torch.nn.utils.clip_grad_norm_'s coefficient;
+ *                                                            1 when max_norm <= 0 (measure only) or n == 0
+ *     state[2] = 1 when the norm is inf or NaN, else 0; then state[1] = 0
+ *     state[3] = 0
+ *   csa_adamw_step_clipped: csa_adamw_step with that state. The step is skipped when clip[2] != 0, exactly
+ *     as for found_inf (torch would write NaN into every parameter instead); otherwise each gradient is
+ *     used as (g * inv_scale) * clip[1], two fp32 multiplies in the order of unscale_ then
+ *     clip_grad_norm_. Gradients are never written. clip == NULL is csa_adamw_step. */
+typedef struct csa_grad_sumsq_args {
+  const csa_adamw_tensor* tensors; /* the three tables of csa_adamw_args */
+  const int32_t* chunk_tensor;
+  const int64_t* chunk_start;
+  int64_t ntensors, nchunks;
+  double* partials;                /* device, at least first + nchunks entries */
+  int64_t first;                   /* >= 0: this call's first slot in partials */
+} csa_grad_sumsq_args;
+
+csa_status csa_grad_sumsq(const csa_grad_sumsq_args* a, void* stream);
+csa_status csa_grad_norm_finish(const double* partials, int64_t n, const float* grad_scale, float max_norm,
+                                float* state, void* stream);
+csa_status csa_adamw_step_clipped(const csa_adamw_args* a, const float* clip, void* stream);
 
 /* ---- Generator head (module/components.py:95-102): logp = log(softmax(dropout(logits), -1)) ----
  * logits/logp/dlogp/dlogits: (rows, V) contiguous fp32. dropout p in [0,1) (0 = eval); the keep mask
