@@ -6,5 +6,6 @@ Public surface:
   csa_amd.module.disentangled_attn DisentangledAttn                         (module/disentangled_attn.py)
   csa_amd.ops                      torch.ops.csa.* custom ops + autograd functions
   csa_amd.data                     synthetic AST batches with the reference's relation encoding
+  csa_amd.batch_ops                ast_batch: a batch's structural fields from parent arrays, on the device
 """
 __version__ = "0.1.0"

@@ -199,6 +199,16 @@ class LapPeArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class AstBatchArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("B", i64), ("N", i64),
+        ("parents", vp), ("num_node", vp),
+        ("L", vp), ("T", vp), ("L_mask", vp), ("T_mask", vp), ("plane_sb", i64),
+        ("adj", vp), ("tree_pos", vp), ("triplet", vp),
+        ("status", vp),
+    ]
+
+
 class CsaSeqMetricsArgs(ctypes.Structure):  # v10 addition
     _fields_ = [
         ("hyp", vp), ("rows", i64), ("Th", i64), ("hyp_stride", i64),
@@ -344,6 +354,10 @@ def lib():
     L.csa_seq_metrics_supported.argtypes = [i64, i64]
     L.csa_seq_metrics.restype = ctypes.c_int
     L.csa_seq_metrics.argtypes = [ctypes.POINTER(CsaSeqMetricsArgs), vp]
+    L.csa_ast_batch_supported.restype = ctypes.c_int  # v10 addition: batch preparation on the device
+    L.csa_ast_batch_supported.argtypes = [i64]
+    L.csa_ast_batch.restype = ctypes.c_int
+    L.csa_ast_batch.argtypes = [ctypes.POINTER(AstBatchArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -380,4 +394,5 @@ EXPORTED_SYMBOLS = (
     "csa_tree_pos_supported", "csa_tree_pos_bwd_workspace_bytes", "csa_tree_pos_fwd", "csa_tree_pos_bwd",
     "csa_lap_pe_supported", "csa_lap_pe",
     "csa_seq_metrics_supported", "csa_seq_metrics",
+    "csa_ast_batch_supported", "csa_ast_batch",
 )

@@ -210,8 +210,32 @@ def collect_fn(batch, nthreads=None):
     return data, target
 
 
+def collate_parents(batch):
+    """collect_fn's counterpart for items that store a parent array instead of the raw L / T matrices: `batch` is a
+    list of (item, _) with item dicts holding src_seq, tgt_seq, target (equal lengths across the batch), num_node and
+    parents, the (n,) or (N,) parent array of the AST (parent[0] = -1, 0 <= parent[v] < v). Returns (namespace, target)
+    with parents (B, N) int32 (N = src_seq's length, -1 beyond an item's array) and num_node (B,) int32 in place of
+    every structural field: 4 N bytes per AST instead of 4 N^2. CSATrans.process_data builds what its use_pegen reads
+    from them on the batch's device (batch_ops.ast_batch)."""
+    from types import SimpleNamespace
+
+    import torch
+    items = [it for it, _ in batch]
+    stack = lambda k: torch.stack([torch.as_tensor(it[k]) for it in items], 0)
+    src = stack("src_seq")
+    N = src.shape[1]
+    parents = torch.full((len(items), N), -1, dtype=torch.int32)
+    for b, it in enumerate(items):
+        p = torch.as_tensor(it["parents"]).to(torch.int32).reshape(-1)[:N]
+        parents[b, :p.numel()] = p
+    target = stack("target")
+    data = SimpleNamespace(src_seq=src, tgt_seq=stack("tgt_seq"), target=target, parents=parents,
+                           num_node=torch.tensor([int(it["num_node"]) for it in items], dtype=torch.int32))
+    return data, target
+
+
 def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None, src_vocab=10000,
-                    tgt_vocab=20000, max_tgt_len=50, native=True, ablation_fields=False):
+                    tgt_vocab=20000, max_tgt_len=50, native=True, ablation_fields=False, planes=True):
     """A batch of synthetic ASTs. Returns a dict of numpy arrays:
 
     L, T (B,N,N) uint8 relation indices; L_mask, T_mask (B,N,N) bool; src_mask (B,N) bool
@@ -219,7 +243,9 @@ def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None,
     num_node; tgt_seq/target (B, max_tgt_len-1) int64 (BOS ... EOS, PAD). Relation planes come from
     the native builder (relation_planes) unless native=False. ablation_fields=True adds what the structure-encoding
     ablations read, built from the same trees: adj (B,N,N) bool (adjacency), tree_pos (B,N,128) fp32
-    (tree_positions) and triplet (B,N) int64 (triplet_ids, a synthetic vocabulary)."""
+    (tree_positions) and triplet (B,N) int64 (triplet_ids, a synthetic vocabulary). planes=False returns, from the same
+    RNG draws, parents (B,N) int32 (-1 beyond num_node) in place of every structural field (L, T, the masks and the
+    ablation fields): the batch that batch_ops.ast_batch completes on the device."""
     rng = np.random.default_rng(seed)
     lo = max_size if min_nodes is None else min_nodes
     hi = max_size if max_nodes is None else max_nodes
@@ -241,6 +267,9 @@ def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None,
         tgt[b, 0] = BOS
         tgt[b, 1:tl + 1] = rng.integers(4, tgt_vocab, tl)
         tgt[b, tl + 1] = EOS
+    src_mask = np.arange(max_size)[None, :] >= nn[:, None]
+    if not planes:
+        return dict(parents=parents, num_node=nn, src_seq=src, src_mask=src_mask, tgt_seq=tgt[:, :-1], target=tgt[:, 1:])
     if native:
         L, T, Lm, Tm = relation_planes(parents, nn, max_size)
     else:  # the Python restatement (tests compare the two)
@@ -252,7 +281,6 @@ def synthetic_batch(batch, max_size=150, seed=1, min_nodes=None, max_nodes=None,
             rl, rt = relation_matrices(parents[b, :n].astype(np.int64), kids, max_size)
             L[b], Lm[b] = collate_relations(rl)
             T[b], Tm[b] = collate_relations(rt)
-    src_mask = np.arange(max_size)[None, :] >= nn[:, None]
     out = dict(L=L, T=T, L_mask=Lm, T_mask=Tm, num_node=nn, src_seq=src, src_mask=src_mask,
                tgt_seq=tgt[:, :-1], target=tgt[:, 1:])
     if ablation_fields:

@@ -147,8 +147,12 @@ class CSE(nn.Module):
 
     def forward(self, data):
         out = data.src_pe_emb
-        rel = torch.stack([data.L, data.T], 1)          # (B,2,N,N) uint8: heads 0-3 read L, 4-7 read T
-        mask = torch.stack([data.L_mask, data.T_mask], 1)
+        rel, mask = getattr(data, "rel", None), getattr(data, "rel_mask", None)
+        if rel is None or mask is None:
+            rel = torch.stack([data.L, data.T], 1)          # (B,2,N,N) uint8: heads 0-3 read L, 4-7 read T
+            mask = torch.stack([data.L_mask, data.T_mask], 1)
+        elif mask.dtype == torch.bool:  # batch_ops.ast_batch's buffers: no copy (the kernels read bytes)
+            mask = mask.view(torch.uint8)
         rel_emb = self.build_rel_emb()
         for layer in self.layers:
             out = layer(out, rel_emb, rel, mask)
@@ -457,7 +461,19 @@ class CSATrans(nn.Module):
             data.tgt_emb = self.tgt_embedding(data.tgt_seq)
 
     def process_data(self, data):
-        """base_seq2seq.py:56-57."""
+        """base_seq2seq.py:56-57. A batch that carries data.parents and data.num_node but no data.L (data.collate_parents,
+        synthetic_batch(planes=False)) gets what this model's use_pegen reads, and nothing more, built on its device by
+        batch_ops.ast_batch: rel / rel_mask (and their L, T, L_mask, T_mask views), adj, tree_pos or triplet. A field
+        the batch already carries is kept."""
+        if getattr(data, "L", None) is None and getattr(data, "parents", None) is not None:
+            from .batch_ops import FIELDS_OF_MODE, ast_batch
+            need = tuple(f for f in FIELDS_OF_MODE[self.use_pegen] if getattr(data, f, None) is None)
+            if self.use_pegen == "laplacian" and getattr(data, "lap_pe", None) is not None:
+                need = ()  # encode takes the precomputed eigenvectors
+            if need:
+                built = vars(ast_batch(data.parents, data.num_node, fields=need))
+                for f in need + tuple(k for k in ("rel", "rel_mask") if k in built):
+                    setattr(data, f, built[f])
         self.base_process(data)
 
     def encode(self, data):
@@ -615,6 +631,12 @@ def label_smoothing_loss(logp, target, padding_idx=PAD):
 def batch_to_device(sb, device):
     """Synthetic batch dict (csa_amd.data.synthetic_batch) -> device-resident namespace."""
     g = lambda k, dt=None: torch.as_tensor(sb[k], dtype=dt).to(device, non_blocking=True)
+    if "L" not in sb:  # synthetic_batch(planes=False): the parent arrays; process_data builds the fields on the device
+        data = SimpleNamespace(src_seq=g("src_seq", torch.int64), tgt_seq=g("tgt_seq", torch.int64),
+                               parents=g("parents", torch.int32), num_node=g("num_node", torch.int32))
+        if "lap_pe" in sb:
+            data.lap_pe = g("lap_pe", torch.float32)
+        return data, g("target", torch.int64)
     data = SimpleNamespace(src_seq=g("src_seq", torch.int64), tgt_seq=g("tgt_seq", torch.int64),
                            L=g("L", torch.uint8), T=g("T", torch.uint8), L_mask=g("L_mask", torch.uint8),
                            T_mask=g("T_mask", torch.uint8))

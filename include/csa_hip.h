@@ -553,6 +553,44 @@ typedef struct csa_lap_pe_args {
 int csa_lap_pe_supported(int64_t N, int64_t pegen_dim);
 csa_status csa_lap_pe(const csa_lap_pe_args* a, void* stream);
 
+/* ---- v10 additions: batch preparation on the device (csrc/csa_batch.hip) ----
+ * Every structural field of a batch of ASTs from parents (B, N) int32 and num_node (B) int32 in one launch, one (or,
+ * for large N, several) workgroups per AST; what the host builds in csa_ast_relations and csa_amd/data.py's
+ * adjacency / tree_positions / triplet_ids, bit for bit. The contract on a tree is the host builder's: parent[0] < 0
+ * and 0 <= parent[v] < v for 0 < v < n, n = num_node[b] clamped to [0, N] (a longer tree is truncated to its first N
+ * nodes); any such topological numbering is accepted, not only pre-order (ancestors are found from an Euler-tour
+ * interval computed in the kernel, never from the ids). Nodes >= n of the parent array are not read.
+ *   depth(v), child_idx(v): the node's depth (root 0) and its rank among its parent's children in increasing id.
+ *   rawL[i][j] = depth(j) - depth(i) when one of i, j is a proper ancestor of the other, else 0;
+ *   rawT[i][j] = child_idx(j) - child_idx(i) for distinct children of one parent, else 0;
+ *   L, T (B, N, N) uint8 = clamp(raw + 75, 0, 149); L_mask, T_mask (B, N, N) bytes = (raw == 0);
+ *   adj (B, N, N) bytes = 1 inside the n x n block where |rawL| <= 1, else 0;
+ *   tree_pos (B, N, 128) fp32: node v's row is its parent's row plus a 1 at 128 - 8 depth + min(child_idx, 7) when
+ *     depth <= 16; the rows of the root and of nodes >= n are zero;
+ *   triplet (B, N) int64 = 2 + min(depth, 15) * 64 + min(child_idx(parent), 7) * 8 + min(child_idx, 7) (the root's
+ *     parent index is 0), 0 (PAD) for nodes >= n.
+ * A NULL output pointer means that field is not built (its memory is not touched). Every parent value is range-checked
+ * before it is used as an index. A malformed tree sets status[b] = 1 (else 0) and gets the fields of the empty tree:
+ * planes 75, masks 1, adj 0, tree_pos 0, triplet PAD; the other ASTs of the batch are unaffected.
+ * The planes may start at any byte address ((B, 2, N, N) buffers with N odd): aligned dword stores with byte stores at a
+ * plane's two ends; each output byte is written exactly once. parents, num_node and status are 4-byte aligned, tree_pos
+ * 16, triplet 8. Deterministic, no atomics, no allocation, no sync: capturable.
+ * Supported: 1 <= N <= 3276 (20 bytes of tables per node within 64 KiB of LDS). The tables are set up by single lanes in
+ * O(n) dependent LDS steps per AST. */
+typedef struct csa_ast_batch_args {
+  int64_t B, N;
+  const int32_t* parents;    /* (B, N) */
+  const int32_t* num_node;   /* (B) */
+  uint8_t* L; uint8_t* T; uint8_t* L_mask; uint8_t* T_mask;   /* (B, N, N) each, or NULL */
+  int64_t plane_sb;          /* batch stride of those four in bytes: 0 = N * N, 2 N * N = halves of (B, 2, N, N) buffers */
+  uint8_t* adj;              /* (B, N, N) or NULL */
+  float* tree_pos;           /* (B, N, 128) or NULL */
+  int64_t* triplet;          /* (B, N) or NULL */
+  int32_t* status;           /* (B) */
+} csa_ast_batch_args;
+int csa_ast_batch_supported(int64_t N);
+csa_status csa_ast_batch(const csa_ast_batch_args* a, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);
