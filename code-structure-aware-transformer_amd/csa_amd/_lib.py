@@ -358,6 +358,12 @@ def lib():
     L.csa_ast_batch_supported.argtypes = [i64]
     L.csa_ast_batch.restype = ctypes.c_int
     L.csa_ast_batch.argtypes = [ctypes.POINTER(AstBatchArgs), vp]
+    L.csa_token_logp_supported.restype = ctypes.c_int  # v10 additions: scoring given tokens (csa_amd/score_ops.py)
+    L.csa_token_logp_supported.argtypes = [i64]
+    L.csa_token_logp_fwd.restype = ctypes.c_int
+    L.csa_token_logp_fwd.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, vp]
+    L.csa_token_logp_bwd.restype = ctypes.c_int
+    L.csa_token_logp_bwd.argtypes = [vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -395,4 +401,5 @@ EXPORTED_SYMBOLS = (
     "csa_lap_pe_supported", "csa_lap_pe",
     "csa_seq_metrics_supported", "csa_seq_metrics",
     "csa_ast_batch_supported", "csa_ast_batch",
+    "csa_token_logp_supported", "csa_token_logp_fwd", "csa_token_logp_bwd",
 )

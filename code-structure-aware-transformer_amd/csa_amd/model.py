@@ -544,14 +544,19 @@ class GreedyGenerator(nn.Module):
 
 _DECODING = ("DecodingConstraints", "_SteppedDecoding", "CachedGreedyGenerator", "BeamSearchGenerator",
              "SamplingGenerator")
+_SCORING = ("SequenceScorer", "rerank", "validation_nll")
 
 
 def __getattr__(name):
     """The names of csa_amd.decoding, exported from here as before they moved. That module imports this one
-    (CachedGreedyGenerator subclasses GreedyGenerator), so it is imported on first use, not while this one loads."""
+    (CachedGreedyGenerator subclasses GreedyGenerator), so it is imported on first use, not while this one loads.
+    The names of csa_amd.scoring (scoring given summaries under the model) are exported the same way."""
     if name in _DECODING:
         from . import decoding
         return getattr(decoding, name)
+    if name in _SCORING:
+        from . import scoring
+        return getattr(scoring, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -591,6 +591,31 @@ typedef struct csa_ast_batch_args {
 int csa_ast_batch_supported(int64_t N);
 csa_status csa_ast_batch(const csa_ast_batch_args* a, void* stream);
 
+/* ---- v10 additions: the log-probability of one given token per row of logits (csrc/csa_score.hip) ----
+ * Teacher-forced scoring without the (rows, V) log-probability tensor of log_softmax + gather. logits (rows, V) fp32
+ * with a row stride ld >= V in elements (4-byte aligned; 16-byte loads where a row's base is 16-byte aligned), target
+ * (rows) int64. With m_r = max_j z[r, j] and S_r = sum_j exp(z[r, j] - m_r), lse_r = m_r + log S_r:
+ *   logp[r] = (z[r, t_r] - m_r) - log S_r, a true log-softmax at the target (never log of softmax: no underflow to
+ *             -inf); a row whose target is ignore_id or lies outside [0, V) is "ignored" and gets logp = 0;
+ *   lse[r]  = the pair {m_r, log S_r}, (rows, 2) fp32, written for every row, ignored ones included. It is kept as the
+ *             unevaluated sum because one fp32 m + log S rounds at the size of m, which exp(z - lse) would turn into a
+ *             relative error of the backward (5e-4 at |z| ~ 1e4).
+ * -inf logits are legal and contribute 0 to S; a -inf target logit gives logp = -inf; a row that holds a NaN gives NaN;
+ * a row of -inf alone gives NaN, as torch.log_softmax does; +inf logits are unspecified.
+ * The backward writes dz[r, j] = g[r] * ([j == t_r] - exp((z[r, j] - m_r) - log S_r)), row stride dz_ld >= V; an
+ * ignored row is written as zeros whatever g[r] holds, NaN included. dz MAY ALIAS logits (dz == logits with
+ * dz_ld == ld: every element is read by the lane that writes it, before the write); any other overlap is not allowed.
+ * Forward launch classes by V, one workgroup per row: register-resident rows of 512 lanes x NG groups of 8 columns for
+ * V <= 4096 NG, NG = 1..6 (thresholds 4096, 8192, 12288, 16384, 20480, 24576), and a two-pass streaming kernel above
+ * 24576. The backward is elementwise given lse: one workgroup per (row, 4096 columns), no classes.
+ * Supported: 1 <= V <= 2^24 (csa_token_logp_supported). rows == 0 or V == 0 returns CSA_OK and launches nothing.
+ * Deterministic (fixed reduction orders), no atomics, no allocation, no sync: capturable. */
+int csa_token_logp_supported(int64_t V);
+csa_status csa_token_logp_fwd(const float* logits, int64_t ld, const int64_t* target, int64_t rows, int64_t V,
+                              int64_t ignore_id, float* logp, float* lse, void* stream);
+csa_status csa_token_logp_bwd(const float* g, const float* logits, int64_t ld, const int64_t* target, const float* lse,
+                              float* dz, int64_t dz_ld, int64_t rows, int64_t V, int64_t ignore_id, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);
