@@ -218,6 +218,30 @@ class CsaSeqMetricsArgs(ctypes.Structure):  # v10 addition
     ]
 
 
+class SeqAttnArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("R", i64), ("H", i64), ("T", i64), ("S", i64), ("hd", i64), ("kv_group", i64),
+        ("q", vp), ("q_sr", i64), ("q_sh", i64), ("q_st", i64),
+        ("k", vp), ("k_sb", i64), ("k_sh", i64), ("k_sn", i64),
+        ("v", vp), ("v_sb", i64), ("v_sh", i64), ("v_sn", i64),
+        ("mask", vp), ("mask_ld", i64),
+        ("mask_mode", ctypes.c_int32), ("causal", ctypes.c_int32),
+        ("scale", f32),
+        ("out", vp), ("lse", vp),
+    ]
+
+
+class SeqAttnBwdArgs(ctypes.Structure):  # v10 addition
+    _fields_ = [
+        ("fwd", ctypes.POINTER(SeqAttnArgs)),
+        ("dout", vp),
+        ("dq", vp), ("dq_sr", i64), ("dq_sh", i64), ("dq_st", i64),
+        ("dk", vp), ("dk_sb", i64), ("dk_sh", i64), ("dk_sn", i64),
+        ("dv", vp), ("dv_sb", i64), ("dv_sh", i64), ("dv_sn", i64),
+        ("workspace", vp),
+    ]
+
+
 SEQ_METRICS_FIELDS = 12  # CSA_SEQ_METRICS_FIELDS: m1..m4, poss1..poss4, len_h, len_r, lcs, valid
 
 
@@ -364,6 +388,14 @@ def lib():
     L.csa_token_logp_fwd.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, vp]
     L.csa_token_logp_bwd.restype = ctypes.c_int
     L.csa_token_logp_bwd.argtypes = [vp, vp, i64, vp, vp, vp, i64, i64, i64, i64, vp]
+    L.csa_seq_attn_supported.restype = ctypes.c_int  # v10 additions: full-sequence decoder attention (seq_attn_ops.py)
+    L.csa_seq_attn_supported.argtypes = [i64, i64, i64]
+    L.csa_seq_attn_bwd_workspace_bytes.restype = ctypes.c_size_t
+    L.csa_seq_attn_bwd_workspace_bytes.argtypes = [i64, i64, i64]
+    L.csa_seq_attn_fwd.restype = ctypes.c_int
+    L.csa_seq_attn_fwd.argtypes = [ctypes.POINTER(SeqAttnArgs), vp]
+    L.csa_seq_attn_bwd.restype = ctypes.c_int
+    L.csa_seq_attn_bwd.argtypes = [ctypes.POINTER(SeqAttnBwdArgs), vp]
     if L.csa_abi_version() != CSA_ABI_VERSION:
         raise CsaError(f"ABI mismatch: library {L.csa_abi_version()} != binding {CSA_ABI_VERSION}")
     _lib = L
@@ -402,4 +434,5 @@ EXPORTED_SYMBOLS = (
     "csa_seq_metrics_supported", "csa_seq_metrics",
     "csa_ast_batch_supported", "csa_ast_batch",
     "csa_token_logp_supported", "csa_token_logp_fwd", "csa_token_logp_bwd",
+    "csa_seq_attn_supported", "csa_seq_attn_bwd_workspace_bytes", "csa_seq_attn_fwd", "csa_seq_attn_bwd",
 )

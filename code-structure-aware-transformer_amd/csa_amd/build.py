@@ -13,7 +13,7 @@ CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 OUT = os.path.join(HERE, "lib", "libcsa_hip.so")
 SOURCES = ["csa_sbm.hip", "csa_rel.hip", "csa_optim.hip", "csa_gen.hip", "csa_glue.hip", "csa_decode.hip", "csa_beam.hip",
            "csa_sample.hip", "csa_constrain.hip", "csa_pe.hip", "csa_metric.hip", "csa_batch.hip", "csa_score.hip",
-           "csa_host.cpp"]
+           "csa_seqattn.hip", "csa_host.cpp"]
 # the C++ TORCH_LIBRARY shim (torch.ops.csa.* of the hot path): host code against the torch headers; its
 # csa_* symbols resolve at load time to the libcsa_hip.so that csa_amd._lib loaded (RTLD_GLOBAL) first
 SHIM = "csa_torch.cpp"

@@ -285,6 +285,42 @@ class MultiheadAttention(nn.MultiheadAttention):
         return F.linear(o, self.out_proj.weight, self.out_proj.bias).view(B, 1, E)
 
 
+    # ---- full-sequence fused attention (scoring given summaries): csa_amd/seq_attn_ops.py ----
+
+    def project_memory_grad(self, memory):
+        """project_memory through the `linear` glue: the same (B, S, 2, H, hd) values, with gradients to the K/V weights
+        (bias gradient on csa_bias_grad) and to the memory, so to the encoder."""
+        B, S, E = memory.shape
+        w_kv, b_kv = self.in_proj_weight[E:], self.in_proj_bias[E:]
+        return linear(memory, w_kv, b_kv).view(B, S, 2, self.num_heads, E // self.num_heads)
+
+    def forward_fused(self, x, memory_kv=None, key_mask=None, causal=False, mask_mode="own", kv_group=1):
+        """forward(need_weights=False) for a batch-first x (R, T, E) on seq_attn_ops.seq_attention, which applies the
+        masks itself from uint8 rows: no float mask, no layout copy, and in the cross-attention no repeated memory.
+
+        Self-attention (memory_kv None): the packed QKV projection of x. Cross-attention: the q projection alone against
+        memory_kv = project_memory_grad(memory), (R / kv_group, S, 2, H, hd): the kv_group rows of an AST read one
+        projection and their dK / dV are summed in the kernel. key_mask (rows, >= keys) uint8 / bool, causal and
+        mask_mode as seq_attention takes them. Returns (R, T, E) batch-first.
+        The kernel has no attention dropout: in training mode with dropout > 0 this call runs
+        F.scaled_dot_product_attention with the explicit mask, expanded K/V and dropout_p = dropout, the distribution
+        forward() has. self.last_fused tells which of the two the last call took."""
+        from .seq_attn_ops import seq_attention, seq_attention_sdpa, split_heads_kv
+        R, T, E = x.shape
+        H = self.num_heads
+        if memory_kv is None:
+            q, k, v = split_heads3(linear(x, self.in_proj_weight, self.in_proj_bias), H)
+        else:
+            q = linear(x, self.in_proj_weight[:E], self.in_proj_bias[:E]).view(R, T, H, E // H).transpose(1, 2)
+            k, v = split_heads_kv(memory_kv)
+        self.last_fused = not (self.training and self.dropout > 0.0)
+        if self.last_fused:
+            o = seq_attention(q, k, v, key_mask, causal, mask_mode, kv_group)
+        else:
+            o = seq_attention_sdpa(q, k, v, key_mask, causal, mask_mode, kv_group, self.dropout)
+        return linear(o, self.out_proj.weight, self.out_proj.bias)
+
+
 class _SplitHeads3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, num_heads):

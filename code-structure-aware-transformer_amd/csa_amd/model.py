@@ -235,6 +235,18 @@ class DecoderLayer(nn.Module):
         tgt, _ = self.sublayer[2](tgt, self.feed_forward)
         return tgt, w
 
+    def forward_fused(self, tgt, memory, tgt_pad=None, memory_key_padding_mask=None, mask_mode="own", kv_group=1):
+        """forward() on batch-first tensors and MultiheadAttention.forward_fused: tgt (R, T, E), memory (B, S, E) with
+        R = B * kv_group, tgt_pad (R, T) uint8 / bool (non-zero = PAD key; the causal mask is implied), the memory mask
+        (B, S). The same three sublayers; the kv_group rows of an AST share one memory projection."""
+        tgt, _ = self.sublayer[0](tgt, lambda x: (self.self_attn.forward_fused(
+            x, key_mask=tgt_pad, causal=True, mask_mode=mask_mode), None))
+        memory_kv = self.multihead_attn.project_memory_grad(memory)
+        tgt, _ = self.sublayer[1](tgt, lambda x: (self.multihead_attn.forward_fused(
+            x, memory_kv=memory_kv, key_mask=memory_key_padding_mask, kv_group=kv_group), None))
+        tgt, _ = self.sublayer[2](tgt, self.feed_forward)
+        return tgt
+
     def step(self, x, cache, i, t):
         """forward() in eval mode for the single position t (an int, or the device counter), x (B, 1, E):
         x + sublayer(norm(x)) three times against layer i's slots of a DecodeCache."""
@@ -286,6 +298,18 @@ class BaseDecoder(nn.Module):
         for mod in self.layers:
             out, w = mod(out, memory, tgt_mask=tgt_mask, memory_key_padding_mask=memory_key_padding_mask)
         return (self.norm(out) if self.norm is not None else out), w
+
+    def forward_fused(self, tgt, memory, tgt_pad=None, memory_key_padding_mask=None, mask_mode="own", kv_group=1):
+        """forward() for batch-first tgt (R, T, E) and an UN-repeated batch-first memory (B, S, E), R = B * kv_group,
+        on the fused full-sequence attention (DecoderLayer.forward_fused): tgt_pad (R, T) uint8 / bool replaces the
+        (R * H, T, T) float mask (mask_mode "own": forward()'s mask.repeat_interleave(H, 0); "reference": its
+        mask.repeat(H, 1, 1)), memory_key_padding_mask is the (B, S) mask. Returns (R, T, E). self.last_fused: every
+        attention of the call ran seq_attention (False: a module in training mode with dropout > 0 took SDPA)."""
+        out = tgt
+        for mod in self.layers:
+            out = mod.forward_fused(out, memory, tgt_pad, memory_key_padding_mask, mask_mode, kv_group)
+        self.last_fused = all(a.last_fused for mod in self.layers for a in (mod.self_attn, mod.multihead_attn))
+        return self.norm(out) if self.norm is not None else out
 
     def empty_cache(self, B, max_len, device, dtype, repeat_heads=False, beam=None, S=None, group=None):
         """A zeroed DecodeCache for B memory rows and up to max_len target positions: the one place that spells the
@@ -544,7 +568,8 @@ class GreedyGenerator(nn.Module):
 
 _DECODING = ("DecodingConstraints", "_SteppedDecoding", "CachedGreedyGenerator", "BeamSearchGenerator",
              "SamplingGenerator")
-_SCORING = ("SequenceScorer", "rerank", "validation_nll")
+_SCORING = ("SequenceScorer", "rerank", "validation_nll", "ATTENTIONS")
+_SEQ_ATTN = ("seq_attention",)
 
 
 def __getattr__(name):
@@ -557,6 +582,9 @@ def __getattr__(name):
     if name in _SCORING:
         from . import scoring
         return getattr(scoring, name)
+    if name in _SEQ_ATTN:  # the fused full-sequence decoder attention behind SequenceScorer(attention="fused")
+        from . import seq_attn_ops
+        return getattr(seq_attn_ops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -15,6 +15,7 @@ from .model import PAD, make_std_mask
 from .score_ops import token_logp
 
 HEAD_MASKS = ("own", "reference")
+ATTENTIONS = ("sdpa", "fused")
 
 
 class SequenceScorer(nn.Module):
@@ -43,10 +44,24 @@ class SequenceScorer(nn.Module):
     candidates, return_tokens=False) starts from a precomputed memory (B, S, E), any device, CPU included (the decoder's
     torch paths and the op's fallback). Both return namespace(logp (B, G) fp32 sums over the scored positions, length
     (B, G) int32 counts of them, tokens (B, G, T') fp32 per-position log-probabilities or None); G is squeezed away for
-    (B, T') input. The sum is a plain sum(-1) of the per-token vector: deterministic."""
+    (B, T') input. The sum is a plain sum(-1) of the per-token vector: deterministic.
 
-    def __init__(self, model, eos_id=EOS, head_mask="own", multi_gpu=False):
+    attention, how the decoder pass runs:
+      "sdpa"   decoder.forward(): torch SDPA with float masks (R * H, T, T) and (R * H, 1, S); with G > 1 candidates
+               per AST the memory and its mask are repeated G times, so every layer projects B * G * S memory rows.
+      "fused"  decoder.forward_fused() on seq_attn_ops.seq_attention (csrc/csa_seqattn.hip): the masks are read in
+               the kernel from the (R, T) PAD bytes and the (B, S) memory mask, and the G rows of an AST read ONE memory
+               projection (kv_group = G), their dK / dV summed in the kernel. No float mask, no repeated memory. The
+               kernel has no attention dropout: a decoder in training mode with dropout > 0 runs its attention calls on
+               SDPA with the distribution of "sdpa" (still without the repeated projection).
+    last_attention: "fused" when every attention of the last call ran the fused op, else "sdpa"; None before a call."""
+
+    def __init__(self, model, eos_id=EOS, head_mask="own", multi_gpu=False, attention="sdpa"):
         super().__init__()
+        if attention not in ATTENTIONS:
+            raise ValueError(f"SequenceScorer: attention must be one of {ATTENTIONS}")
+        self.attention = attention
+        self.last_attention = None
         if head_mask not in HEAD_MASKS:
             raise ValueError(f"SequenceScorer: head_mask must be one of {HEAD_MASKS}")
         if eos_id is not None and (isinstance(eos_id, bool) or int(eos_id) != eos_id or eos_id < 0):
@@ -85,6 +100,14 @@ class SequenceScorer(nn.Module):
         input ids dec_in (B * group, T), targets (B * group, T) and the bool mask of the positions to score ->
         (B * group, T) fp32 log-probabilities, 0 where not scored."""
         m = self.model
+        if self.attention == "fused":
+            dec = m.decoder.forward_fused(m.tgt_embedding(dec_in), enc, (dec_in == PAD).to(torch.uint8),
+                                          None if src_mask is None else src_mask.to(torch.uint8),
+                                          mask_mode=self.head_mask, kv_group=group)
+            self.last_attention = "fused" if m.decoder.last_fused else "sdpa"
+            logits = m.generator.linear(dec)
+            return token_logp(logits, torch.where(scored, target, torch.full_like(target, -1)), ignore_id=-1)
+        self.last_attention = "sdpa"
         H = m.decoder.layers[0].self_attn.num_heads
         mask = make_std_mask(dec_in, PAD)
         tgt_mask = mask.repeat(H, 1, 1) if self.head_mask == "reference" else mask.repeat_interleave(H, 0)
@@ -113,14 +136,14 @@ def rerank(ids, out, length_penalty=0.0):
     return best, order
 
 
-def validation_nll(model, batches, head_mask="reference"):
+def validation_nll(model, batches, head_mask="reference", attention="sdpa"):
     """Token-level negative log-likelihood and perplexity over (data, target) batches: data.tgt_seq is the decoder input
     and the non-PAD positions of target (B, T) are scored, so with head_mask="reference" this is the number
     label_smoothing_loss(model(data)[0], target) reports at smoothing 0 for one batch, wherever that one is finite,
     pooled over all tokens of all batches. -> namespace(nll, ppl, tokens): Python floats and the token count. The
     log-probabilities are summed in fp64 on the device; one host sync, at the end. Runs under no_grad in the model's
-    current mode (call model.eval() first for validation)."""
-    scorer = SequenceScorer(model, eos_id=None, head_mask=head_mask)
+    current mode (call model.eval() first for validation). attention: as SequenceScorer takes it."""
+    scorer = SequenceScorer(model, eos_id=None, head_mask=head_mask, attention=attention)
     m = scorer.model
     total = count = None
     with torch.no_grad():

@@ -616,6 +616,52 @@ csa_status csa_token_logp_fwd(const float* logits, int64_t ld, const int64_t* ta
 csa_status csa_token_logp_bwd(const float* g, const float* logits, int64_t ld, const int64_t* target, const float* lse,
                               float* dz, int64_t dz_ld, int64_t rows, int64_t V, int64_t ignore_id, void* stream);
 
+/* ---- v10 additions: full-sequence (teacher-forced) decoder attention, forward and backward (csrc/csa_seqattn.hip) ----
+ *   out[r, i, h*hd : (h+1)*hd] = sum_j softmax_j(scale * q[r,h,i] . K[kb,h,j] + m(r,h,i,j)) * V[kb,h,j],  kb = r / kv_group
+ * fp32 throughout. q is (R,H,T,hd) and K / V are (R / kv_group,H,S,hd) through their element strides, hd contiguous: the
+ * strided views of a packed (B,T,3,H,hd) or (B,S,2,H,hd) projection are read in place; the kv_group query rows of an
+ * AST read ONE K/V. out is (R,T,H*hd) contiguous, lse (R,H,T) the row log-sum-exp of the scaled, masked scores, saved
+ * for the backward. m is -inf on a masked key and 0 elsewhere; key j is masked for query i of (r, h) when
+ *   causal is set and j > i (causal requires S == T and kv_group == 1), or
+ *   mask (optional uint8 rows of mask_ld >= S bytes) holds a non-zero byte at column j of row
+ *     mask_mode 0: r / kv_group        (a (B,S) memory mask; with kv_group == 1 a row's own PAD columns)
+ *     mask_mode 1: (r * H + h) % R     (the head-repeated target mask of the reference decode, DecodeCache.head_pad).
+ * A query row whose keys are all masked gives NaN in out (0/0, as SDPA and the decode-step kernel) and lse = -inf; its
+ * own gradients are unspecified, its contribution to dk / dv is exact zeros, and neither pass faults on it.
+ * Backward: dout (R,T,H*hd) contiguous; dq, dk, dv are written through their own strides (hd contiguous), so they may
+ * be slices of one packed gradient buffer. dk / dv have K / V's shape: the sum over the kv_group rows and the T queries
+ * of an AST is taken inside the kernel, rows and query tiles in ascending order; a key that is masked for every query
+ * gets exact zeros. workspace: the byte count the workspace query returns (rowsum(dout * out), (R,H,T) fp32).
+ * Supported: hd in {8, 64}, 1 <= T <= 256, S >= 1, R * H * ceil(max(T, S) / 16) below 2^31; 16 x 16 tiles on
+ * v_mfma_f32_16x16x4_f32, one wave per workgroup, one launch forward and two backward. Every pointer 16-byte aligned
+ * (lse, workspace: 4), every stride a non-negative multiple of 4 elements. Deterministic (fixed summation orders, no
+ * atomics), no allocation, no sync: capturable. */
+typedef struct csa_seq_attn_args {
+  int64_t R, H, T, S, hd, kv_group;
+  const float* q; int64_t q_sr, q_sh, q_st;   /* (R,H,T,hd) */
+  const float* k; int64_t k_sb, k_sh, k_sn;   /* (R / kv_group,H,S,hd) */
+  const float* v; int64_t v_sb, v_sh, v_sn;
+  const uint8_t* mask; int64_t mask_ld;       /* NULL, or rows of mask_ld >= S bytes */
+  int32_t mask_mode, causal;
+  float scale;                                /* hd^-0.5 */
+  float* out;                                 /* (R,T,H*hd) contiguous */
+  float* lse;                                 /* (R,H,T) */
+} csa_seq_attn_args;
+
+typedef struct csa_seq_attn_bwd_args {
+  const csa_seq_attn_args* fwd;               /* the forward's arguments, out and lse as it wrote them */
+  const float* dout;                          /* (R,T,H*hd) contiguous */
+  float* dq; int64_t dq_sr, dq_sh, dq_st;
+  float* dk; int64_t dk_sb, dk_sh, dk_sn;
+  float* dv; int64_t dv_sb, dv_sh, dv_sn;
+  void* workspace;
+} csa_seq_attn_bwd_args;
+
+int csa_seq_attn_supported(int64_t hd, int64_t T, int64_t S);
+size_t csa_seq_attn_bwd_workspace_bytes(int64_t R, int64_t H, int64_t T);
+csa_status csa_seq_attn_fwd(const csa_seq_attn_args* a, void* stream);
+csa_status csa_seq_attn_bwd(const csa_seq_attn_bwd_args* b, void* stream);
+
 /* ---- Linear bias gradient: db[c] (+)= sum_r dy[r, c], dy (rows, cols) contiguous fp32 ----
  * Two passes (row-slice partials into the caller's workspace, then a fixed-order sum): deterministic. */
 size_t csa_bias_grad_workspace_bytes(int64_t rows, int64_t cols);

@@ -8,8 +8,17 @@
 and the op alone at the same (rows, V): token_logp against torch.log_softmax(...).gather(...), forward and
 forward + backward, between HIP events, with torch.cuda.max_memory_allocated above the inputs for each.
 
+With --fused, the legs of the fused full-sequence decoder attention instead (profiles/seq_score_fused.json):
+
+  sdpa / fused   SequenceScorer(attention=...) at G = 1 and 4, forward under no_grad and forward + backward of
+                 logp.sum() to the decoder, the generator and the encoder output, with the peak memory of each
+  seq_attention  the op alone against F.scaled_dot_product_attention with the explicit -inf masks and expanded K/V
+                 (seq_attn_ops.seq_attention_sdpa), at the cross-attention shape (R = batch * G, T, S = nodes,
+                 kv_group = G, a memory mask) and the self-attention shape (causal, a row's own PAD columns), forward
+                 and forward + backward between HIP events
+
 usage: python tools/bench_score.py [--batch 64] [--nodes 150] [--max-tgt-len 50] [--calls 3] [--reps 5]
-                                   [--out profiles/seq_score.json]
+                                   [--out profiles/seq_score.json] [--fused [--fused-out profiles/seq_score_fused.json]]
 
 Both legs live in one process on one GPU and are timed alternately: per rep, every leg runs `calls` scoring calls
 between two device synchronisations on the host clock. The JSON keeps the median of the reps, every rep and the
@@ -65,6 +74,99 @@ def resolved(a, b):
     return abs(a["median"] - b["median"]) > max(a["spread"], b["spread"])
 
 
+def fused_legs(a, model, enc, src_mask, cands, res):
+    """The --fused legs (module docstring) into res["groups"] and res["op"]."""
+    from csa_amd.data import EOS
+    from csa_amd.model import PAD, SequenceScorer
+    from csa_amd.seq_attn_ops import seq_attention, seq_attention_sdpa
+    legs = ("sdpa", "fused")
+    scorers = {leg: SequenceScorer(model, eos_id=EOS, head_mask="own", attention=leg) for leg in legs}
+    H = model.decoder.layers[0].self_attn.num_heads
+    hd = enc.shape[-1] // H
+    dev = enc.device
+    for G, cand in cands.items():
+        def fwd(leg):
+            with torch.no_grad():
+                return scorers[leg].score(enc, src_mask, cand).logp
+
+        def fwd_bwd(leg):
+            model.zero_grad(set_to_none=True)
+            e = enc.detach().requires_grad_()
+            scorers[leg].score(e, src_mask, cand).logp.sum().backward()
+            return e.grad
+
+        def run(fn, leg, n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                fn(leg)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / n
+
+        out = {"max_abs_difference_of_scores": float((fwd("sdpa") - fwd("fused")).abs().max()),
+               "max_abs_difference_of_enc_grad": float((fwd_bwd("sdpa") - fwd_bwd("fused")).abs().max()),
+               "last_attention": scorers["fused"].last_attention, "rows": cand.shape[0] * G * cand.shape[2]}
+        for key, fn in (("fwd_ms", fwd), ("fwd_bwd_ms", fwd_bwd)):
+            for leg in legs:
+                run(fn, leg, 2)
+            ms = {leg: [] for leg in legs}
+            for _ in range(a.reps):
+                for leg in legs:
+                    ms[leg].append(run(fn, leg, a.calls))
+            out[key] = {leg: summary(ms[leg]) for leg in legs}
+            for leg in legs:
+                out[key][leg]["peak_bytes"] = peak_bytes(lambda: fn(leg))
+            out[key]["fused_minus_sdpa_ms"] = out[key]["fused"]["median"] - out[key]["sdpa"]["median"]
+            out[key]["resolved"] = resolved(out[key]["fused"], out[key]["sdpa"])
+        model.zero_grad(set_to_none=True)
+        res["groups"][f"G={G}"] = out
+
+        # the op alone: the cross-attention and the self-attention of one layer at this G
+        R, T, S = a.batch * G, cand.shape[2], enc.shape[1]
+        pad = (cand.reshape(R, T) == PAD).to(torch.uint8)
+        pad[:, 0] = 0  # the decoder input starts with BOS
+        shapes = {"cross": dict(k_rows=a.batch, S=S, key_mask=src_mask.to(torch.uint8), causal=False, kv_group=G),
+                  "self": dict(k_rows=R, S=T, key_mask=pad, causal=True, kv_group=1)}
+        op_out = {}
+        for name, sh in shapes.items():
+            q = torch.randn(R, H, T, hd, device=dev)
+            k, v = (torch.randn(sh["k_rows"], H, sh["S"], hd, device=dev) for _ in range(2))
+            g = torch.randn(R, T, H * hd, device=dev)
+            kw = dict(key_mask=sh["key_mask"], causal=sh["causal"], mask_mode="own", kv_group=sh["kv_group"])
+            ops = {"seq_attention": lambda *t: seq_attention(*t, **kw), "sdpa": lambda *t: seq_attention_sdpa(*t, **kw)}
+            leaves = [t.clone().requires_grad_() for t in (q, k, v)]
+
+            def op_fwd(fn):
+                with torch.no_grad():
+                    return fn(q, k, v)
+
+            def op_fwd_bwd(fn):
+                for t in leaves:
+                    t.grad = None
+                fn(*leaves).backward(g)
+
+            timed = {(n, key): (lambda fn=fn, f=f: f(fn)) for n, fn in ops.items()
+                     for key, f in (("fwd_ms", op_fwd), ("fwd_bwd_ms", op_fwd_bwd))}
+            op_ms = {key: [] for key in timed}
+            for fn in timed.values():
+                fn()
+            for _ in range(a.reps):
+                for key, fn in timed.items():
+                    op_ms[key] += events_ms(fn, 1)
+            o = {n: {key: summary(op_ms[n, key]) for key in ("fwd_ms", "fwd_bwd_ms")} for n in ops}
+            for n, fn in ops.items():
+                o[n]["fwd_peak_bytes"] = peak_bytes(lambda: op_fwd(fn))
+                o[n]["fwd_bwd_peak_bytes"] = peak_bytes(lambda: op_fwd_bwd(fn))
+            for t in leaves:
+                t.grad = None
+            for key in ("fwd_ms", "fwd_bwd_ms"):
+                o[key + "_resolved"] = resolved(o["seq_attention"][key], o["sdpa"][key])
+            o["max_abs_difference"] = float((op_fwd(ops["seq_attention"]) - op_fwd(ops["sdpa"])).abs().max())
+            o["shape"] = {"R": R, "H": H, "T": T, "S": sh["S"], "hd": hd, "kv_group": sh["kv_group"]}
+            op_out[name] = o
+        res["op"][f"G={G}"] = op_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -74,6 +176,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seq_score.json"))
+    ap.add_argument("--fused", action="store_true", help="the legs of the fused full-sequence decoder attention")
+    ap.add_argument("--fused-out", default=os.path.join(ROOT, "profiles", "seq_score_fused.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_score: needs the GPU (no CPU timing is meaningful)")
@@ -118,12 +222,27 @@ def main():
         "groups": {}, "op": {},
     }
     g = torch.Generator().manual_seed(a.seed)
+    cands = {}
     for G in GROUPS:
         cand = torch.randint(4, V, (a.batch, G, T), generator=g)
         ends = torch.randint(5, T, (a.batch, G), generator=g)
         col = torch.arange(T)[None, None, :]
         cand = torch.where(col == ends[:, :, None], torch.full_like(cand, EOS), cand)
-        cand = torch.where(col > ends[:, :, None], torch.full_like(cand, PAD), cand).to(dev)
+        cands[G] = torch.where(col > ends[:, :, None], torch.full_like(cand, PAD), cand).to(dev)
+    if a.fused:
+        res["what"] = ("teacher-forced scoring of G candidates per AST from a precomputed encoder output, eval mode: "
+                       "SequenceScorer(attention='fused') against attention='sdpa', forward under no_grad and forward + "
+                       "backward; ms per call, host clock between device syncs, legs alternated, median of reps; then "
+                       "seq_attention alone against SDPA with explicit masks between HIP events")
+        fused_legs(a, model, enc, src_mask, cands, res)
+        os.makedirs(os.path.dirname(os.path.abspath(a.fused_out)), exist_ok=True)
+        with open(a.fused_out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps(res))
+        return
+    for G in GROUPS:
+        cand = cands[G]
         fns = {"generator": lambda: generator_leg(cand), "scorer": lambda: scorer.score(enc, src_mask, cand).logp}
 
         def run(leg, n):
