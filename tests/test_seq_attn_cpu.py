@@ -1,8 +1,10 @@
 """The full-sequence decoder attention without a GPU (tests/seq_attn_ref.py): the torch fallback of
 seq_attn_ops.seq_attention against the fp64 oracle, forward and gradients; wrong variants of the rule leave the bound on
-the chosen cases; SequenceScorer(attention="fused") on CPU tensors against the loop oracle and against "sdpa", values and
+the chosen cases, and so does an operand read with its neighbour's strides; build() is bit for bit stable for the old
+cases; the wide-logit and one-visible-key cases are what the GPU tests take them for; SequenceScorer(attention="fused") on CPU tensors against the loop oracle and against "sdpa", values and
 gradients; which path a call reports; argument checks; the C ABI's host-side validation."""
 import ctypes
+import hashlib
 
 import numpy as np
 import pytest
@@ -35,6 +37,20 @@ def test_fallback_matches_the_oracle_forward_and_gradients(name):
     ("causal_own_hd8_T17", "other_mode", ("out", "dq", "dk", "dv")),
     ("causal_reference_hd8_T17", "other_mode", ("out", "dq", "dk", "dv")),
     ("group_hd8_G3", "one_member", ("dk", "dv")),
+    ("group4_own_hd8", "group_mod", ("out", "dq", "dk", "dv")),
+    ("group4_own_hd8", "other_mode", ("out", "dq", "dk", "dv")),
+    ("group4_own_hd64", "one_member", ("dk", "dv")),
+    ("group4_reference_hd8", "group_mod", ("out", "dq", "dk", "dv")),
+    ("group4_reference_hd8", "other_mode", ("out", "dq", "dk", "dv")),
+    ("group4_reference_hd64", "other_mode", ("out", "dq", "dk", "dv")),
+    ("group2_reference_hd8", "group_mod", ("out", "dq", "dk", "dv")),
+    ("group2_reference_hd8", "other_mode", ("out", "dq", "dk", "dv")),
+    ("group2_reference_hd64", "other_mode", ("out", "dq", "dk", "dv")),
+    ("heads3_hd8", "other_mode", ("out", "dq", "dk", "dv")),
+    ("mask_prefix_hd8", "mask_row0", ("out", "dq", "dk", "dv")),
+    ("mask_prefix_hd64", "mask_row0", ("out", "dq", "dk", "dv")),
+    ("mask_alternate_hd8", "mask_row0", ("out", "dq", "dk", "dv")),
+    ("long_causal_reference_hd64_T256", "other_mode", ("out", "dq", "dk", "dv")),
 ])
 def test_wrong_variants_leave_the_bound(name, wrong, tensors):
     """A fixture is decisive when an answer computed by a plausible wrong rule lies outside the case's bound."""
@@ -44,6 +60,87 @@ def test_wrong_variants_leave_the_bound(name, wrong, tensors):
     for tname, x, x64, base in zip(("out", "dq", "dk", "dv"), bad, good, ref.BASELINE[name]):
         if tname in tensors:
             assert ref.rel_err(x, x64) > 1000 * ref.FACTOR * base, (name, wrong, tname)
+
+
+@pytest.mark.parametrize("name", ["layout_cross_hd8", "layout_causal_hd64"])
+@pytest.mark.parametrize("which", ["k", "v", "q"])
+def test_reading_one_operand_with_anothers_strides_leaves_the_bound(name, which):
+    """The mixed-layout GPU tests are decisive: with one operand stored as (N, L, H, hd) and read with the contiguous
+    (N, H, L, hd) strides of its neighbour, as a kernel that took k's strides for v would, every tensor leaves the bound
+    (dv = P^T dO does not depend on V's values: it is exempt when V is the misread one)."""
+    c = ref.CASES[name]
+    inputs = ref.build(c)
+    i = "qkv".index(which)
+    stored = inputs[i].transpose(1, 2).contiguous().transpose(1, 2)  # the same values, the other layout
+    assert torch.equal(stored, inputs[i])
+    misread = stored.as_strided(stored.shape, inputs[i].stride())
+    bad = ref.oracle(c, *(misread if j == i else t for j, t in enumerate(inputs)))
+    for tname, x, x64, base in zip(("out", "dq", "dk", "dv"), bad, ref.oracle(c, *inputs), ref.BASELINE[name]):
+        if (which, tname) != ("v", "dv"):
+            assert ref.rel_err(x, x64) > 1000 * ref.FACTOR * base, (name, which, tname)
+
+
+def test_build_is_unchanged_for_the_old_cases():
+    """The keys build() gained default to off: the old cases' tensors are bit for bit what they were (sha256 over
+    q, k, v, mask, dout, taken before the keys existed), and their BASELINE rows are the old ones."""
+    want = {"group_hd8_G2": "60aea848df2961e94820fc410a5e3ebce349609acfca0f9df97769675b8784c5",
+            "packed_self_hd64": "f0d178a8c9d4b8a6a3abeb8a94efe3097e114e38565b3dc5ca15de8792e0237b",
+            "causal_reference_hd8_T17": "3b2b66ccce88ac6e17700db57aa02f5b8c00d4dfc46d277ce46aeda6c51f7293",
+            "packed_cross_hd8": "a35e8a7ee0cfc4bacb92f1ebc8f5643b95cf7c0ddf2aa51e4a5eb1a0a0145abb"}
+    for name, digest in want.items():
+        h = hashlib.sha256()
+        for t in ref.build(ref.CASES[name]):
+            h.update(t.contiguous().numpy().tobytes())
+        assert h.hexdigest() == digest, name
+    assert len(ref.OLD_CASES) == 38 and list(ref.CASES)[:38] == [c["name"] for c in ref.OLD_CASES]
+    assert all(c["qscale"] is None and c["key_order"] is None and c["dout"] is None for c in ref.OLD_CASES)
+    assert set(ref.BASELINE) == set(ref.CASES)
+    assert ref.BASELINE["cross_hd8_T1_S17"] == (1.941e-07, 1.772e-07, 7.696e-08, 1.890e-07)
+    assert ref.BASELINE["packed_cross_hd64"] == (4.917e-07, 5.454e-07, 5.951e-07, 4.400e-07)
+
+
+@pytest.mark.parametrize("name", [n for n, c in ref.CASES.items() if c["qscale"] is not None])
+def test_wide_logit_cases_are_wide_ordered_and_finite(name):
+    c = ref.CASES[name]
+    q, k, v, mask, dout = inputs = ref.build(c)
+    s = (q.double() @ k.double().transpose(-1, -2)) * float(c["hd"]) ** -0.5
+    assert 6.0 < s.std().item() < 10.0  # scale * s: a standard deviation of about 8
+    step = s[:, :, 0, 1:] - s[:, :, 0, :-1]  # query 0 against the sorted keys
+    assert bool((step >= 0).all() if c["key_order"] == "ascending" else (step <= 0).all())
+    gap = (s[:, :, 0, -1] - s[:, :, 0, 0]).abs()  # first to last key: exp(-gap) lies below fp32's resolution
+    assert gap.min().item() > -np.log(ref.EPS32), gap
+    assert not bool(ref.mask_entries(c, mask).all(-1).any())  # no query row is fully masked
+    for x in ref.oracle(c, *inputs):
+        assert bool(torch.isfinite(x).all()), name
+    for n, e in ref.lse_bound(c, *inputs).items():
+        assert 0.0 < e < 1e-4, (name, n, e)
+
+
+@pytest.mark.parametrize("name", ["mask_last_only_hd8", "mask_last_only_hd64"])
+def test_one_visible_last_key_gives_that_v_row_and_zero_dq_dk(name):
+    """What the GPU test relies on: in fp64 out is exactly the last V row for every query, dq and dk are identically
+    zero (the zero_bound branch of check()), dv is non-zero in that row only."""
+    c = ref.CASES[name]
+    q, k, v, mask, dout = inputs = ref.build(c)
+    out, dq, dk, dv = ref.oracle(c, *inputs)
+    want = v[:, :, c["S"] - 1].double().reshape(c["R"], 1, -1).expand(-1, c["T"], -1)
+    assert torch.equal(out, want)
+    assert not bool(dq.any()) and not bool(dk.any())
+    assert bool(dv[:, :, c["S"] - 1].any()) and not bool(dv[:, :, :c["S"] - 1].any())
+    assert ref.BASELINE[name][1] is None and ref.BASELINE[name][2] is None and ref.BASELINE[name][0] == 0.0
+    assert ref.zero_bound(c, q, k, v, dout) > 0.0
+
+
+def test_new_mask_kinds_are_what_their_names_say():
+    for name, rows in (("mask_prefix_hd8", {0: range(32), 1: range(16)}), ("mask_alternate_hd8", {0: range(0, 33, 2), 1: range(1, 33, 2)}),
+                       ("mask_last_only_hd8", {0: range(32), 1: range(32)})):
+        mask = ref.build(ref.CASES[name])[3]
+        for b, dead in rows.items():
+            assert mask[b].nonzero().flatten().tolist() == list(dead), (name, b)
+    for name in ("group4_reference_hd8", "group2_reference_hd64"):  # (R, S), the rows all different
+        c = ref.CASES[name]
+        mask = ref.build(c)[3]
+        assert mask.shape == (c["R"], c["S"]) and len({tuple(r.tolist()) for r in mask}) == c["R"]
 
 
 def test_scorer_case_separates_the_two_mask_modes():
@@ -193,6 +290,13 @@ def test_abi_validates_on_the_host():
                                  (dict(q_st=6), 1, b"multiples of 4"),
                                  (dict(mask=p, mask_ld=4), 1, b"mask_ld"),
                                  (dict(mask_mode=2), 1, b"mask_mode"),
+                                 (dict(mask=p, mask_ld=5, S=6, causal=0), 1, b"mask_ld"),
+                                 (dict(k_sn=10), 1, b"multiples of 4"),
+                                 (dict(v_sh=42), 1, b"multiples of 4"),
+                                 (dict(q_sr=-80), 1, b"multiples of 4"),
+                                 (dict(q=ctypes.c_void_p(p.value + 4)), 1, b"16-byte aligned"),
+                                 (dict(v=ctypes.c_void_p(p.value + 8)), 1, b"16-byte aligned"),
+                                 (dict(R=6, kv_group=4), 1, b"kv_group must divide R"),
                                  (dict(out=None), 1, b"null pointer"),
                                  (dict(R=1 << 30, H=1 << 10), 2, b"grid limit")):
         a = _lib.SeqAttnArgs(**{**ok, **change})
@@ -201,3 +305,8 @@ def test_abi_validates_on_the_host():
     a = _lib.SeqAttnArgs(**ok)
     b = _lib.SeqAttnBwdArgs(fwd=ctypes.pointer(a), dout=p, dq=p, dk=p, dv=p)  # no workspace
     assert L.csa_seq_attn_bwd(ctypes.byref(b), None) == 1 and b"null pointer" in L.csa_last_error_str()
+    for change, text in ((dict(dq=ctypes.c_void_p(p.value + 4)), b"16-byte aligned"), (dict(dv_sn=6), b"multiples of 4"),
+                         (dict(dk_sh=-40), b"multiples of 4")):
+        b = _lib.SeqAttnBwdArgs(**{**dict(fwd=ctypes.pointer(a), dout=p, dq=p, dk=p, dv=p, workspace=p, dq_sr=80, dq_sh=40,
+                                          dq_st=8, dk_sb=80, dk_sh=40, dk_sn=8, dv_sb=80, dv_sh=40, dv_sn=8), **change})
+        assert L.csa_seq_attn_bwd(ctypes.byref(b), None) == 1 and text in L.csa_last_error_str(), change

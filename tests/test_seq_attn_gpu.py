@@ -1,7 +1,10 @@
 """The full-sequence decoder attention on the GPU (csrc/csa_seqattn.hip through seq_attn_ops.seq_attention): every case
-of tests/seq_attn_ref.py against the fp64 oracle within four times the parent's error, forward and the three gradients;
-packed operands and packed gradients; exact zeros at masked keys; bitwise determinism; a fully masked query row;
+of tests/seq_attn_ref.py against the fp64 oracle within four times the parent's error, forward and the three gradients
+(16 and 19 key tiles, G = 4, odd head counts, masked leading tiles, wide logits among them); packed operands and packed
+gradients; exact zeros at masked keys; operands, masks and upstream gradients handed over in other layouts; no store
+outside the addressed output elements; bitwise determinism; a fully masked query row;
 SequenceScorer(attention="fused") on the tiny model against the loop oracle, "sdpa" and the beam's scores; peak memory."""
+import ctypes
 import functools
 
 import numpy as np
@@ -58,6 +61,10 @@ def test_kernels_match_the_oracle_forward_and_gradients(name):
         assert bool(dead.any()) or c["T"] == 1  # one position: BOS, never PAD
         for g in (dk, dv):
             assert bool((g.transpose(1, 2)[dead] == 0).all()), name
+    if c["mask"] == "last_only":  # p = 1, l = 1: out is the last V row of the AST and head, bit for bit
+        v = inputs[2]
+        want = v[:, :, c["S"] - 1].repeat_interleave(c["G"], 0).reshape(c["R"], 1, -1).expand(-1, c["T"], -1)
+        assert torch.equal(out.cpu().view(torch.int32), want.contiguous().view(torch.int32)), name
     if c["packed"] and c["causal"]:
         assert packed_qkv(dq, dk, dv), "dq, dk, dv are not the views of one packed gradient"
     elif c["packed"]:
@@ -124,6 +131,177 @@ def test_fully_masked_query_row_gives_nan_in_that_row_only():
     other = [r for r in range(c["R"]) if r != 2]
     for g in got[1:]:  # the rows that do not read row 2's keys are untouched by it
         assert bool(torch.isfinite(g[other]).all())
+
+
+# ---- the same values in other layouts ----
+
+LAYOUT_CASES = [n for n in ref.CASES if n.startswith("layout_") and not n.endswith("_doutrow")]
+
+
+@functools.lru_cache(maxsize=None)
+def _layout_case(name):
+    """Case, CPU inputs, fp64 oracle and the plain tensors on the GPU: computed once, never modified."""
+    c = ref.CASES[name]
+    inputs = ref.build(c)
+    return c, inputs, ref.oracle(c, *inputs), _to_gpu(c, inputs)
+
+
+def _transposed(t):
+    """The same (N, H, L, hd) values stored as (N, L, H, hd): a head-major view with other strides."""
+    return t.transpose(1, 2).contiguous().transpose(1, 2)
+
+
+def _offset1(t):
+    """The same values as a view of a flat buffer that starts at element 1: 4 bytes off every alignment."""
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    flat[1:].copy_(t.reshape(-1))
+    return flat[1:].view(t.shape)
+
+
+def _padded(t):
+    """The same values as the slice [..., :hd] of a tensor whose last dimension is hd + 2: row stride hd + 2."""
+    wide = torch.zeros(*t.shape[:-1], t.shape[-1] + 2, dtype=t.dtype, device=t.device)
+    wide[..., :t.shape[-1]] = t
+    return wide[..., :t.shape[-1]]
+
+
+def _run_spied(c, q, k, v, mask, dout, monkeypatch):
+    """_run, also returning the (q, k, v) that reached _SeqAttn.apply."""
+    from csa_amd import seq_attn_ops
+    seen, real = [], seq_attn_ops._SeqAttn.apply
+    monkeypatch.setattr(seq_attn_ops._SeqAttn, "apply", staticmethod(lambda *a: (seen.append(a[:3]), real(*a))[1]))
+    got = _run(c, (q, k, v, mask, dout))
+    assert len(seen) == 1
+    return got, seen[0]
+
+
+@pytest.mark.parametrize("which, form", [(w, f) for f in ("transposed", "offset1", "padded") for w in "qkv"])
+@pytest.mark.parametrize("name", LAYOUT_CASES)
+def test_one_operand_in_another_layout(name, which, form, monkeypatch):
+    """ONE of q, k, v in another layout, the other two contiguous: k and v (or q and the output rows) then have different
+    strides, and a kernel that read one with the other's would leave the bound. A transposed operand is read in place;
+    one that is misaligned or has a row stride that is no multiple of 4 is copied."""
+    from csa_amd.seq_attn_ops import _operand
+    c, inputs, want, (q, k, v, mask, dout) = _layout_case(name)
+    ops = dict(q=q, k=k, v=v)
+    plain = ops[which]
+    t = dict(transposed=_transposed, offset1=_offset1, padded=_padded)[form](plain)
+    assert torch.equal(t, plain) and (form == "offset1" or t.stride() != plain.stride())
+    ops[which] = t
+    got, seen = _run_spied(c, ops["q"], ops["k"], ops["v"], mask, dout, monkeypatch)
+    for n, passed in zip("qkv", seen):
+        in_place = n != which or form == "transposed"
+        assert (_operand(ops[n]) is ops[n]) == in_place, (n, form)
+        assert (passed.data_ptr() == ops[n].data_ptr()) == in_place, (n, form)
+        assert passed.data_ptr() % 16 == 0 and passed.stride(-1) == 1 and not any(s % 4 for s in passed.stride()[:-1])
+        if in_place:
+            assert passed.stride() == ops[n].stride()
+    ref.check(c, got, inputs, want, what=f"{which} {form} ")
+
+
+@pytest.mark.parametrize("form", ["bool", "wide", "wide_view"])
+@pytest.mark.parametrize("name", LAYOUT_CASES)
+def test_key_mask_forms_are_bitwise_equal(name, form):
+    """torch.bool, (rows, S + 5) with the columns past S all set (ignored), and its [:, :S] view (row stride above S):
+    the same bits as the plain uint8 (rows, S) run in out and the three gradients."""
+    c, _, _, (q, k, v, mask, dout) = _layout_case(name)
+    S = c["S"]
+    wide = torch.cat([mask, torch.ones(mask.shape[0], 5, dtype=torch.uint8, device="cuda")], 1)
+    other = dict(bool=mask.bool(), wide=wide, wide_view=wide[:, :S])[form]
+    assert form != "wide_view" or (other.stride(0) == S + 5 and other.shape == mask.shape)
+    a, b = _run(c, (q, k, v, mask, dout)), _run(c, (q, k, v, other, dout))
+    for x, y in zip(a, b):
+        assert torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)), (name, form)
+
+
+@pytest.mark.parametrize("name", LAYOUT_CASES)
+def test_non_contiguous_upstream_gradient(name):
+    """dout with the same values and other strides, and (the _doutrow case) a stride-0 expansion of one row."""
+    c, inputs, want, (q, k, v, mask, dout) = _layout_case(name)
+    other = dout.transpose(1, 2).contiguous().transpose(1, 2)
+    assert torch.equal(other, dout) and (c["T"] == 1 or other.stride() != dout.stride())
+    ref.check(c, _run(c, (q, k, v, mask, other)), inputs, want, what="dout transposed ")
+    c, inputs, want, (q, k, v, mask, _) = _layout_case(name + "_doutrow")
+    row = inputs[4][:1, :1].contiguous().cuda().expand(c["R"], c["T"], -1)
+    assert row.stride() == (0, 0, 1) and torch.equal(row.cpu(), inputs[4])
+    ref.check(c, _run(c, (q, k, v, mask, row)), inputs, want, what="dout expanded ")
+
+
+# ---- nothing is stored outside the outputs ----
+
+SENTINEL = 0x7FA5C3E1  # as fp32 a NaN with a payload no result carries; compared as int32
+GUARD = 64  # sentinel floats before and after every tensor
+
+
+def _carve(shape, strides):
+    """-> (int32 sentinel buffer, fp32 view of `shape` / `strides` inside it after GUARD elements, bool map of the
+    addressed elements)."""
+    span = sum((n - 1) * s for n, s in zip(shape, strides)) + 1
+    buf = torch.full((GUARD + (span + 3) // 4 * 4 + GUARD,), SENTINEL, dtype=torch.int32, device="cuda")
+    t = buf.view(torch.float32).as_strided(shape, strides, GUARD)
+    addressed = torch.zeros(buf.shape, dtype=torch.bool, device="cuda")
+    addressed.as_strided(shape, strides, GUARD).fill_(True)
+    assert t.data_ptr() % 16 == 0 and int(addressed.sum()) == t.numel()
+    return buf, t, addressed
+
+
+def _stray_cases():
+    out = []
+    for hd in (8, 64):
+        for T in (1, 17):
+            for S in (1, 17, 33):
+                out.append(ref.case(f"stray_cross_hd{hd}_T{T}_S{S}", 4, 2, hd, T, S, G=2, mask="memory" if S > 1 else None,
+                                    seed=1000 + len(out)))
+        out.append(ref.case(f"stray_causal_hd{hd}_T17", 2, 2, hd, 17, 17, causal=True, mask="pad", seed=1000 + len(out)))
+    return {c["name"]: c for c in out}
+
+
+STRAY_CASES = _stray_cases()
+
+
+@pytest.mark.parametrize("name", list(STRAY_CASES))
+def test_no_store_outside_the_addressed_output_elements(name):
+    """csa_seq_attn_fwd / _bwd through the C ABI with out, lse, the workspace and the gradients carved out of
+    sentinel-filled buffers: guards of 64 floats around each, and for the gradients a T / S stride of H * hd + 8, a head
+    stride of hd + 4 and spare elements between rows of the batch. Every sentinel outside the addressed elements survives
+    (for hd = 8 the other half of the 16-wide head-dim tile would land in the gap after the head), every addressed
+    element is written, and the values are the bits seq_attention gives with outputs of its own."""
+    from csa_amd import _lib
+    c = STRAY_CASES[name]
+    R, H, hd, T, S, G = (c[n] for n in ("R", "H", "hd", "T", "S", "G"))
+    B, row = R // G, H * hd + 8
+    q, k, v, mask, dout = gpu = _to_gpu(c, ref.build(c))
+    want = _run(c, gpu)
+    bufs = dict(out=_carve((R, T, H * hd), (T * H * hd, H * hd, 1)),
+                lse=_carve((R, H, T), (H * T, T, 1)),
+                ws=_carve((R, H, T), (H * T, T, 1)),
+                dq=_carve((R, H, T, hd), (T * row + 16, hd + 4, row, 1)),
+                dk=_carve((B, H, S, hd), (S * row + 16, hd + 4, row, 1)),
+                dv=_carve((B, H, S, hd), (S * row + 32, hd + 4, row, 1)))
+    t = {n: b[1] for n, b in bufs.items()}
+    assert H * (hd + 4) <= row  # the heads of a row and their spare elements fit below the next row
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    L = _lib.lib()
+    a = _lib.SeqAttnArgs(R=R, H=H, T=T, S=S, hd=hd, kv_group=G,
+                         q=p(q), q_sr=q.stride(0), q_sh=q.stride(1), q_st=q.stride(2),
+                         k=p(k), k_sb=k.stride(0), k_sh=k.stride(1), k_sn=k.stride(2),
+                         v=p(v), v_sb=v.stride(0), v_sh=v.stride(1), v_sn=v.stride(2),
+                         mask=p(mask) if mask is not None else None, mask_ld=mask.stride(0) if mask is not None else 0,
+                         mask_mode=0, causal=int(c["causal"]), scale=float(hd) ** -0.5, out=p(t["out"]), lse=p(t["lse"]))
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(L.csa_seq_attn_fwd(ctypes.byref(a), stream), "csa_seq_attn_fwd")
+    b = _lib.SeqAttnBwdArgs(fwd=ctypes.pointer(a), dout=p(dout), workspace=p(t["ws"]),
+                            dq=p(t["dq"]), dq_sr=t["dq"].stride(0), dq_sh=t["dq"].stride(1), dq_st=t["dq"].stride(2),
+                            dk=p(t["dk"]), dk_sb=t["dk"].stride(0), dk_sh=t["dk"].stride(1), dk_sn=t["dk"].stride(2),
+                            dv=p(t["dv"]), dv_sb=t["dv"].stride(0), dv_sh=t["dv"].stride(1), dv_sn=t["dv"].stride(2))
+    _lib.check(L.csa_seq_attn_bwd(ctypes.byref(b), stream), "csa_seq_attn_bwd")
+    torch.cuda.synchronize()
+    for n, (buf, _, addressed) in bufs.items():
+        written = buf != SENTINEL
+        assert not bool((written & ~addressed).any()), f"{name}: a store outside {n}"
+        assert bool(written[addressed].all()), f"{name}: {n} has elements that were never written"
+    for n, x in zip(("out", "dq", "dk", "dv"), want):
+        assert torch.equal(t[n].contiguous().view(torch.int32), x.contiguous().view(torch.int32)), (name, n)
 
 
 # ---- the scorer on the tiny model ----
