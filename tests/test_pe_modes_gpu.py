@@ -117,6 +117,57 @@ def test_tree_pos_kernels_match_fp64_autograd(shape, F, binary, zero_p):
         assert torch.equal(o[:, 0, :, 0], q[:, 0] * torch.tensor(128 * F / 2).sqrt())
 
 
+@pytest.mark.parametrize("shape,F,binary,zero_p", [c for c in TP_CASES if c[0] == (1, 65)])
+def test_tree_pos_bwd_workspace_guards_poison_written(shape, F, binary, zero_p):
+    """csa_tree_pos_bwd's workspace contract (tests/abi_arena.py, the method of tests/test_sbm_abi_guard_gpu.py) at the
+    smallest TP_CASES row count with several row blocks (65 rows: two blocks of TP_BWD_ROWS = 64, the second with one
+    row): out, dp and the workspace carved at exactly csa_tree_pos_bwd_workspace_bytes between guards, prefilled 0x00
+    and 0xFF; dp bitwise equal either way and bitwise the module's."""
+    import ctypes
+    import os
+    from abi_arena import POISON_ONES, POISON_ZERO, Arena
+    from conftest import PKG
+    from csa_amd._lib import check, lib
+    from csa_amd.model import TreePositionalEncodings
+    with open(os.path.join(PKG, "csrc", "csa_pe.hip")) as f:
+        assert "constexpr int TP_BWD_ROWS = 64;" in f.read()
+    L = lib()
+    pos, p, dout = pe_ref.tree_pos_case(shape, F, seed=1000 * shape[1] + F, binary=binary, zero_p=zero_p)
+    rows, depth, width = shape[0] * shape[1], 16, 8
+    assert 64 < rows < 128
+    inp = [t.reshape(rows, -1).contiguous().cuda() if t.dim() > 1 else t.cuda() for t in (pos, p, dout)]
+    host = [t.cpu().clone() for t in inp]
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    runs = {}
+    for poison in (POISON_ZERO, POISON_ONES):
+        ar = Arena("cuda", capacity=4 << 20, poison=poison)
+        out = ar.carve("out", shape=(rows, depth * width * F), align=16)
+        dp = ar.carve("dp", shape=(F,))
+        ws = ar.carve("workspace", nbytes=L.csa_tree_pos_bwd_workspace_bytes(rows, depth, width, F))
+        check(L.csa_tree_pos_fwd(vp(inp[0]), vp(inp[1]), vp(out), rows, depth, width, F, float(128 * F), stream),
+              "csa_tree_pos_fwd")
+        ar.assert_guards_intact("tree_pos fwd")
+        check(L.csa_tree_pos_bwd(vp(inp[0]), vp(inp[1]), vp(inp[2]), vp(dp), rows, depth, width, F, float(128 * F), vp(ws),
+                                 stream), "csa_tree_pos_bwd")
+        ar.assert_guards_intact("tree_pos bwd")
+        if poison == POISON_ONES:
+            ar.assert_written(out, "out")
+            ar.assert_written(dp, "dp")
+        runs[poison] = (out.cpu(), dp.cpu())
+    bits = lambda t: t.contiguous().view(torch.int32)
+    for a, b in zip(runs[POISON_ZERO], runs[POISON_ONES]):
+        assert torch.equal(bits(a), bits(b)), "the result depends on the buffers' old bytes"
+    assert all(torch.equal(bits(t.cpu()), bits(h)) for t, h in zip(inp, host))
+    enc = TreePositionalEncodings(16, 8, F, 128 * F).cuda()
+    with torch.no_grad():
+        enc.p.copy_(p)
+    ref = enc(pos.cuda())
+    ref.backward(dout.cuda())
+    assert torch.equal(bits(ref.detach().cpu().reshape(rows, -1)), bits(runs[POISON_ONES][0]))
+    assert torch.equal(bits(enc.p.grad.cpu()), bits(runs[POISON_ONES][1]))
+
+
 # ---- the model ----
 
 def _model_and_data(mode, z, tgt=True):

@@ -386,6 +386,92 @@ def test_bias_grad_scalar_path_of_a_4_byte_aligned_dy_is_bitwise_the_vector_path
     _close(got, dy.double().sum(0), "column sums", scaled=True)
 
 
+# ---- D2. the workspace contracts of csa_bias_grad and csa_layernorm_bwd: guards, poison, written ----
+# (tests/abi_arena.py; the method of tests/test_sbm_abi_guard_gpu.py: outputs and workspace carved at exactly the
+# byte counts the size queries return, between guards, prefilled 0x00 and then 0xFF)
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _same_bits(a, b):
+    return torch.equal(a.cpu().contiguous().view(torch.int32), b.cpu().contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("rows,cols", [(255, 65), (1, 4)])
+def test_bias_grad_workspace_guards_poison_written(rows, cols):
+    from abi_arena import POISON_ONES, POISON_ZERO, Arena
+    from csa_amd._lib import check, lib
+    L = lib()
+    g = torch.Generator().manual_seed(rows + cols)
+    dy = torch.randn(rows, cols, generator=g).cuda()
+    pre = (torch.randn(cols, generator=g) * 10).cuda()
+    dy0 = dy.clone()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    runs = {}
+    for poison in (POISON_ZERO, POISON_ONES):
+        ar = Arena("cuda", capacity=1 << 20, poison=poison)
+        db = ar.carve("db", shape=(cols,))
+        acc = ar.carve("db_acc", shape=(cols,))
+        ws = ar.carve("workspace", nbytes=L.csa_bias_grad_workspace_bytes(rows, cols))
+        check(L.csa_bias_grad(_vp(dy), _vp(db), rows, cols, 0, _vp(ws), stream), "csa_bias_grad")
+        ar.assert_guards_intact(f"bias_grad {rows}x{cols} accumulate=0")
+        ar.fill("workspace", poison)
+        acc.copy_(pre)
+        check(L.csa_bias_grad(_vp(dy), _vp(acc), rows, cols, 1, _vp(ws), stream), "csa_bias_grad")
+        ar.assert_guards_intact(f"bias_grad {rows}x{cols} accumulate=1")
+        if poison == POISON_ONES:
+            ar.assert_written(db, "db")
+            ar.assert_written(acc, "db (accumulate)")
+        runs[poison] = (db.cpu(), acc.cpu())
+    assert all(_same_bits(a, b) for a, b in zip(runs[POISON_ZERO], runs[POISON_ONES])), "db depends on the workspace's old bytes"
+    assert _same_bits(dy, dy0)
+    assert torch.equal(runs[POISON_ONES][0], _bias_grad_abi(dy, torch.empty(cols, device="cuda"), rows, cols, 0).cpu())
+    _close(runs[POISON_ONES][0], dy.double().sum(0).cpu(), "column sums", scaled=True)
+
+
+@pytest.mark.parametrize("cols,cpl", [(252, 1), (260, 2), (516, 3), (772, 4)])
+def test_layernorm_bwd_workspace_guards_poison_written(cols, cpl, monkeypatch):
+    """One width per CPL whose last chunk is partial (LN_COLS), 33 rows (a partial group of 4, a partial workgroup of
+    32): y, stats, dx, dgamma, dbeta and the workspace between guards; bitwise glue.LayerNorm on the same inputs."""
+    from abi_arena import POISON_ONES, POISON_ZERO, Arena
+    from csa_amd._lib import check, lib
+    L = lib()
+    assert (cols, cpl) in LN_COLS and ln_cpl(cols) == cpl and cols % 256
+    rows = 33
+    g = torch.Generator().manual_seed(1000 * rows + cols)
+    x = torch.randn(rows, cols, generator=g) * 3 + 1
+    w, b = torch.randn(cols, generator=g), torch.randn(cols, generator=g)
+    gy = torch.randn(rows, cols, generator=g)
+    inp = [t.cuda() for t in (x, w, b, gy)]
+    xd, wd, bd, gyd = inp
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    runs = {}
+    for poison in (POISON_ZERO, POISON_ONES):
+        ar = Arena("cuda", capacity=4 << 20, poison=poison)
+        out = {"y": ar.carve("y", shape=(rows, cols), align=16), "stats": ar.carve("stats", shape=(rows, 2)),
+               "dx": ar.carve("dx", shape=(rows, cols), align=16), "dgamma": ar.carve("dgamma", shape=(cols,)),
+               "dbeta": ar.carve("dbeta", shape=(cols,))}
+        ws = ar.carve("workspace", nbytes=L.csa_layernorm_bwd_workspace_bytes(rows, cols))
+        check(L.csa_layernorm_fwd(_vp(xd), _vp(wd), _vp(bd), _vp(out["y"]), _vp(out["stats"]), rows, cols, 1e-5, stream),
+              "csa_layernorm_fwd")
+        ar.assert_guards_intact(f"layernorm fwd {rows}x{cols}")
+        check(L.csa_layernorm_bwd(_vp(gyd), _vp(xd), _vp(out["stats"]), _vp(wd), _vp(out["dx"]), _vp(out["dgamma"]),
+                                  _vp(out["dbeta"]), rows, cols, _vp(ws), stream), "csa_layernorm_bwd")
+        ar.assert_guards_intact(f"layernorm bwd {rows}x{cols}")
+        if poison == POISON_ONES:
+            for n, t in out.items():
+                ar.assert_written(t, n)
+        runs[poison] = {n: t.cpu() for n, t in out.items()}
+    for n in runs[POISON_ONES]:
+        assert _same_bits(runs[POISON_ZERO][n], runs[POISON_ONES][n]), f"{n} depends on the buffers' old bytes"
+    for t, h in zip(inp, (x, w, b, gy)):
+        assert _same_bits(t, h)
+    anchor = _ln_run(x, w, b, gy, monkeypatch)
+    for n, t in zip(("y", "dx", "dgamma", "dbeta"), anchor):
+        assert _same_bits(runs[POISON_ONES][n], t), f"{n} differs from glue.LayerNorm"
+
+
 # ---- E. the scalar loads of the scan kernels ----
 
 def _distinct_rows(rows, V, seed):
